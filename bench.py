@@ -20,7 +20,8 @@ the single-GPU run" is checked inside the bench (`parity_vs_single_gpu`).  `--gp
 N ranks itself (child processes, before anything touches the GPU).
   --config c3   32 tracks (seeds 100-131) over the ranks present, K = 32 / N per rank
   --config c5   BASELINE configs[4]: one 30-min track per step (240 chunks, 480 U-Net items)
-Rank 0 prints ONE JSON line.
+  --dump-outputs DIR   what the last timed step returned, as DIR/<name>.npy (dump_outputs), for comparing two builds
+Rank 0 prints ONE JSON line; `ms_per_step` is the timed region's wall time over the K timed steps.
 """
 from __future__ import annotations
 
@@ -265,6 +266,86 @@ def framewise_accounting(n: int) -> dict:
             "framewise_passes": [{"wave": r[0], "kernel": r[1], "yields": r[2], "wave_reads": r[3], "other_bytes": int(r[4]), "reference": r[5]} for r in rows]}
 
 
+DUMP_LIMIT_BYTES = 64 << 20           # --dump-outputs: everything written, all files together
+DUMP_STEM_SAMPLES = 1 << 22           # per stem: 16 MiB of float32 (a 240 s stem is 10.6 M samples)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_sample_positions(n: int) -> np.ndarray:
+    """The stem positions --dump-outputs writes for a stem of n samples: all of them up to DUMP_STEM_SAMPLES, else
+    DUMP_STEM_SAMPLES distinct positions drawn by np.random.default_rng(DUMP_SAMPLE_SEED), sorted (the same for the same n)."""
+    if n <= DUMP_STEM_SAMPLES:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, DUMP_STEM_SAMPLES, replace=False))
+
+
+def _dump_array(name: str, value) -> np.ndarray:
+    """float32 stays float32, other numbers become float64 (sample indices are exact there); anything else is an error."""
+    a = np.asarray(value)
+    if a.dtype == np.float32 or a.dtype == np.float64:
+        return a
+    if a.dtype.kind in "biu":
+        return a.astype(np.float64)
+    raise TypeError(f"bench.py --dump-outputs: output {name!r} is not numeric (dtype {a.dtype})")
+
+
+def dump_outputs(res: dict, out_dir: Path) -> dict:
+    """`--dump-outputs DIR`: what `SeamlessSplitter.split_track` handed its caller for the last timed step, one DIR/<name>.npy per
+    array, so that two builds run with the same arguments (same seeded tracks, same seeded weights) can be compared output for
+    output.  A stem longer than DUMP_STEM_SAMPLES is written as `<stem>_sampled`, its samples at dump_sample_positions.  Lists
+    of records become one row per record, dicts of numbers one file per entry.  An output the step did not produce, or produced
+    empty (no suppressed cut points, no VAD segments, ...), writes no file; a listed output that is not numeric is an error.
+    Left out: timings (`timings*`, the stage times in `gpu_meta`), `device_state` (the device copies of the stems written
+    here), constants (`precision_guard_threshold_ms`), labels (`mode`, `note`, `backend_used`, `pauses[].pause_type`) and
+    the nested VPBD / lyrics reports of vpbd modes, whose selected times are `vpbd_selected_times`."""
+    arrays = {}
+
+    def put(name, value):
+        if value is None:
+            return
+        a = _dump_array(name, value)
+        if a.size:
+            arrays[name] = np.ascontiguousarray(a)
+
+    def adjustments(key):
+        return [[a.raw_time, a.guard_time, a.final_time, a.score, a.guard_shift_ms, a.final_shift_ms] for a in res.get(key) or []]
+
+    for key in ("vocal_track", "instrumental_track"):
+        stem = res.get(key)
+        if stem is None:
+            continue
+        stem = np.asarray(stem).reshape(-1)
+        if stem.size > DUMP_STEM_SAMPLES:
+            put(key + "_sampled", stem[dump_sample_positions(stem.size)])
+        else:
+            put(key, stem)
+    for key in ("sample_boundaries", "refine_boundaries", "cuts_samples", "cuts_sec", "segment_vocal_flags", "segment_spans",
+                "segment_durations", "segment_layout_applied", "suppressed_cut_points_sec", "cut_candidates", "vpbd_selected_times",
+                "num_pauses", "separation_confidence", "precision_guard_ok", "single_segment"):
+        put(key, res.get(key))
+    for k, v in sorted((res.get("guard_shift_stats") or {}).items()):
+        put("guard_shift_stats_" + k, v)
+    put("pauses", [[p.start_time, p.end_time, p.duration, p.confidence, p.cut_point] for p in res.get("pauses") or []])
+    put("guard_adjustments", adjustments("guard_adjustments"))
+    put("guard_adjustments_unfiltered", adjustments("guard_adjustments_unfiltered"))
+    put("vad_segments", [[s["start"], s["end"]] for s in res.get("vad_segments") or []])
+    cache = res.get("feature_cache")
+    if cache is not None:
+        for f in ("rms_series", "spectral_flatness", "onset_envelope", "onset_strength", "onset_frames", "beat_times", "tempo_curve",
+                  "mdd_series", "rms_max", "onset_max", "global_mdd"):
+            put("feature_cache_" + f, getattr(cache, f))
+        bpm = cache.bpm_features
+        if bpm is not None:
+            put("feature_cache_bpm", [bpm.main_bpm, bpm.beat_strength, bpm.bpm_confidence, bpm.tempo_variance])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {"dir": str(out_dir), "files": len(arrays), "bytes": int(total)}
+
+
 C3_SEED0 = 100                         # SURVEY.md 8d: C3 = 32 x C2 with seeds 100-131
 C3_GOLDEN = ROOT / "tests" / "golden" / "c3_n1_sha1.json"
 
@@ -285,7 +366,7 @@ def _launch_ranks(n: int, argv: list) -> int:
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (tracks) per rank, default 3; --config c3 times its 32 tracks, 32 / N per rank")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5"), default="c2",
                     help="c2: 4-min tracks, K per rank (default; N > 1 deals the C3 seeds); c3: exactly the 32 C3 tracks over the ranks; "
@@ -307,7 +388,18 @@ def main() -> None:
                          "queueing; 0: each worker on its own stream, the gate held until the U-Net has left the GPU (round 2's scheme)")
     ap.add_argument("--write-golden", default=None, metavar="PATH",
                     help="(c3, N = 1) write the per-track SHA-1 table of this run to PATH (committed as tests/golden/c3_n1_sha1.json)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all (the stems as a fixed seeded sample); inputs are seeded, so two builds "
+                         "run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.config == "c3" and args.steps is not None and args.steps != 32 // max(1, args.gpus):
+        raise SystemExit(f"bench.py: --config c3 times its 32 tracks, {32 // max(1, args.gpus)} per rank on {args.gpus} GPU(s): "
+                         f"--steps {args.steps} does not match (leave it out or pass that number)")
+    if args.steps is None:
+        args.steps = 3
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.items_per_forward is None:
         args.items_per_forward = 32 if args.config == "c4" else 64
 
@@ -443,6 +535,7 @@ def main() -> None:
 
     if rank == 0:
         res = step_results[-1]
+        dumped = dump_outputs(res, Path(args.dump_outputs)) if args.dump_outputs else None
         total_audio = track_s * steps * world
         flops = spec.flops_per_item() * items
         achieved = flops / (unet_ms / 1e3) / 1e12 if unet_ms > 0 else 0.0
@@ -544,6 +637,8 @@ def main() -> None:
         if world == 1 and args.cpu_baseline_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, weights, spec)
         out["socket_under_load"] = socket_state
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()

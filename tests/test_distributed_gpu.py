@@ -23,15 +23,25 @@ def _free_port() -> int:
 
 
 @pytest.mark.gpu
-def test_bench_distributed_branch_on_rccl_with_one_rank():
+def test_bench_distributed_branch_on_rccl_with_one_rank(tmp_path):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()),
                AC_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    dump = tmp_path / "dump"
     p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--track-seconds", "40",
-                        "--cpu-baseline-seconds", "0"], env=env, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
+                        "--cpu-baseline-seconds", "0", "--dump-outputs", str(dump)], env=env, capture_output=True, text=True, timeout=600,
+                       cwd=str(ROOT))
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["batch_completion"]["backend"] == "nccl"
     assert line["batch_completion"]["summaries_gathered"] == 1 and line["tracks_completed"] == 1
+    # --dump-outputs on the real split_track result: float files, none empty, the stems whole (40 s is under the sample size)
+    import numpy as np
+    files = {f.stem: np.load(f) for f in dump.glob("*.npy")}
+    assert line["dump_outputs"]["files"] == len(files) and line["dump_outputs"]["bytes"] == sum(a.nbytes for a in files.values())
+    assert all(a.dtype in (np.float32, np.float64) and a.size for a in files.values())
+    assert files["vocal_track"].shape == files["instrumental_track"].shape == (40 * 44100,)
+    assert files["sample_boundaries"][0] == 0 and files["sample_boundaries"][-1] == 40 * 44100
+    assert files["feature_cache_rms_series"].size > 0 and files["separation_confidence"].shape == (1,)
 
 
 @pytest.mark.gpu
