@@ -437,9 +437,12 @@ class Context:
         librosa.feature.rms(y=x[a:b], frame, hop)[0]; center=False: windows from the segment start, the last zero padded."""
         self._chk_f32(x)
         a = np.asarray(seg_start, dtype=np.int64); b = np.asarray(seg_end, dtype=np.int64)
-        counts = (1 + (b - a) // hop) if center else -((a - b) // hop)
+        # librosa's frame count of the zero-padded segment (an odd frame has one sample less padding than frame - 1)
+        counts = np.maximum(0, 1 + (b - a + 2 * (frame // 2) - frame) // hop) if center else -((a - b) // hop)
         off = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
         nf = int(off[-1])
+        if nf == 0:
+            return [np.zeros(0, dtype=np.float32) for _ in range(len(a))]
         out = torch.empty(nf, dtype=torch.float32, device=self.device)
         da, db_, do = self.to_device(a), self.to_device(b), self.to_device(off)
         _check(self.lib.ac_segment_frame_rms(self._h, _ptr(x), x.numel(), _ptr(da), _ptr(db_), _ptr(do), len(a), frame, hop, int(center),
@@ -566,7 +569,7 @@ class Context:
     def zero_crossing_rate(self, x: torch.Tensor, frame_len: int, hop: int) -> np.ndarray:
         self._chk_f32(x)
         n = x.numel()
-        nf = 1 + n // hop
+        nf = 1 + (n + 2 * (frame_len // 2) - frame_len) // hop      # librosa's count: an odd frame_len has one sample less padding
         out = torch.empty(nf, dtype=torch.float64, device=self.device)
         _check(self.lib.ac_zero_crossing_rate(self._h, _ptr(x), n, frame_len, hop, _ptr(out), nf, _stream()))
         return out.cpu().numpy()

@@ -395,7 +395,9 @@ __global__ __launch_bounds__(256) void k_zcr(const float* __restrict__ x, int64_
 extern "C" int ac_zero_crossing_rate(ac_ctx* ctx, const float* x, int64_t n, int frame_len, int hop, double* out, int64_t n_frames,
                                      void* stream) {
     AC_REQUIRE(ctx && x && out, "null pointer");
-    AC_REQUIRE(n > 0 && frame_len > 1 && hop > 0 && n_frames == 1 + n / hop, "n_frames != 1 + n/hop");
+    AC_REQUIRE(n > 0 && frame_len > 1 && hop > 0, "sizes must be positive");
+    // librosa's frame count: the track padded by frame_len / 2 on each side, framed by frame_len
+    AC_REQUIRE(n_frames == 1 + (n + 2 * (int64_t)(frame_len / 2) - frame_len) / hop, "n_frames != 1 + (n + 2 (frame_len / 2) - frame_len) / hop");
     hipLaunchKernelGGL(k_zcr, dim3((unsigned)((n_frames + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, n, frame_len, hop, out, n_frames);
     AC_LAUNCH_CHECK();
     return AC_OK;

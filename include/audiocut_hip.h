@@ -263,7 +263,8 @@ int ac_pyin_viterbi(ac_ctx* ctx, const double* logv, const double* logu, int64_t
  * 512 points, scipy.signal.find_peaks(height = 10 % of max); out_count[f] peaks found, out_mag[f][3] the lowest three. */
 int ac_lpc_formants(ac_ctx* ctx, const float* x, int64_t n, int frame_len, int hop, int order, float preemph, int* out_count,
                     double* out_mag, int64_t n_frames, void* stream);
-/* librosa.feature.zero_crossing_rate (edge-padded centred frames); out f64 [1 + n/hop]. */
+/* librosa.feature.zero_crossing_rate (edge-padded centred frames); out f64 [1 + (n + 2 * (frame_len / 2) - frame_len) / hop]
+ * (1 + n/hop for an even frame_len; one less for an odd frame_len when hop divides n, as librosa). */
 int ac_zero_crossing_rate(ac_ctx* ctx, const float* x, int64_t n, int frame_len, int hop, double* out, int64_t n_frames,
                           void* stream);
 /* librosa.feature.spectral_centroid (n_fft 2048) and the low-third magnitude ratio of

@@ -351,3 +351,72 @@ def test_resampling_filter_meets_the_soxr_hq_specification():
     x = np.random.default_rng(0).standard_normal(3000).astype(np.float32)
     assert ORS.resample(x, 16000, 44100).shape == (-(-3000 * 160 // 441),)          # librosa / resample_poly length rule
     assert np.array_equal(ORS.resample(x, 5, 5), x)
+
+
+# every export of include/audiocut_hip.h -> the GPU test that calls it directly and compares it with a reference ("module::test"), or
+# "host-only" (context and error plumbing, size queries, the host C++ beat DP: tested on the CPU above)
+EXPORT_TESTS = {
+    "ac_abi_version": "host-only",
+    "ac_last_error": "host-only",
+    "ac_ctx_create": "host-only",
+    "ac_ctx_destroy": "host-only",
+    "ac_next_leq_scratch": "host-only",
+    "ac_tempogram_parts": "host-only",
+    "ac_local_valley_tiles": "host-only",
+    "ac_host_beat_dp": "host-only",
+    "ac_frame_rms": "test_kernels_gpu::test_frame_rms",
+    "ac_frame_rms_multi": "test_kernels_gpu::test_frame_rms_multi_is_the_single_kernel_bit_for_bit",
+    "ac_stft2048_features": "test_kernels_gpu::test_stft_flatness_and_mel",
+    "ac_onset_strength": "test_kernels_gpu::test_onset_strength",
+    "ac_tempogram_reduce": "test_kernels_gpu::test_tempogram_reduce",
+    "ac_yin_f0": "test_kernels_gpu::test_yin_f0_autocorrelation_kernel",
+    "ac_moving_meansq_db_f64": "test_kernels_gpu::test_moving_meansq_db_and_next_leq",
+    "ac_next_leq_scan": "test_kernels_gpu::test_moving_meansq_db_and_next_leq",
+    "ac_window_argmin_f64": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
+    "ac_zero_cross_nearest": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
+    "ac_quiet_guard_slow": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
+    "ac_pause_cut_points": "test_kernels_gpu::test_pause_cut_points",
+    "ac_mdx_stft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
+    "ac_mdx_istft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
+    "ac_mdx_assemble_ola": "test_kernels_gpu::test_mdx_stft_istft_assemble",
+    "ac_mdx_chunk_vocal": "test_kernels_edges_gpu::test_mdx_chunk_vocal_edges",
+    "ac_sum_squares": "test_kernels_edges_gpu::test_mean_square_partials_edges",
+    "ac_window_sum_squares": "test_kernels_gpu::test_window_mean_squares_is_the_per_window_mean_square_bit_for_bit",
+    "ac_conv3x3_f16x3": "test_unet_gpu::test_conv3x3_f16x3_kernel",
+    "ac_conv3x3_f16x3_w96": "test_unet_gpu::test_conv3x3_f16x3_w96_kernel",
+    "ac_conv3x3_f16x3_s8": "test_kernels_edges_gpu::test_level0_conv_at_64_items_matches_2_items",
+    "ac_conv3x3_f16x3_first": "test_unet_gpu::test_first_conv_fused_into_the_3x3_loader_is_bit_identical",
+    "ac_conv1x1_small": "test_unet_gpu::test_conv1x1_small_kernel",
+    "ac_tdf_linear_f16x3": "test_unet_gpu::test_tdf_linear_f16x3_kernel",
+    "ac_tdf_small_fused": "test_unet_gpu::test_tdf_small_fused_kernel",
+    "ac_down2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
+    "ac_up2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
+    "ac_pyin_observe": "test_kernels_edges_gpu::test_pyin_edges",
+    "ac_pyin_viterbi": "test_kernels_edges_gpu::test_pyin_edges",
+    "ac_lpc_formants": "test_kernels_edges_gpu::test_lpc_formants_edges",
+    "ac_zero_crossing_rate": "test_kernels_edges_gpu::test_zero_crossing_rate_edges",
+    "ac_stft2048_spectral": "test_kernels_edges_gpu::test_stft2048_spectral_edges",
+    "ac_segment_frame_rms": "test_kernels_edges_gpu::test_segment_frame_rms_edges",
+    "ac_segment_sumsq_peak": "test_kernels_edges_gpu::test_segment_sumsq_peak_edges",
+    "ac_local_valley": "test_kernels_edges_gpu::test_local_valley_edges",
+    "ac_resample_poly": "test_export_loader::test_resample_poly_kernel_vs_oracle",
+    "ac_resample_poly_segments": "test_kernels_edges_gpu::test_resample_poly_segments_edges",
+    "ac_pack_pcm24": "test_export_loader::test_pack_pcm24_kernel_vs_host",
+    "ac_silero_frontend": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
+    "ac_silero_lstm": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
+    "ac_silero_out": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
+}
+
+
+def test_every_export_names_its_direct_test():
+    """A new export fails here until someone names the GPU test that calls it directly and compares it with a reference."""
+    import ast
+    header = (ROOT / "include" / "audiocut_hip.h").read_text()
+    assert set(EXPORT_TESTS) == set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", header))
+    defined = {}
+    for ref in set(EXPORT_TESTS.values()) - {"host-only"}:
+        module, name = ref.split("::")
+        if module not in defined:
+            tree = ast.parse((ROOT / "tests" / f"{module}.py").read_text())
+            defined[module] = {node.name for node in tree.body if isinstance(node, ast.FunctionDef)}
+        assert name in defined[module], f"{ref} does not exist"

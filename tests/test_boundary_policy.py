@@ -138,3 +138,31 @@ def test_sample_level_split_tiles_the_track():
         assert pieces[0][0] == 0 and pieces[-1][1] == n and all(a[1] == b[0] for a, b in zip(pieces, pieces[1:]))
         assert len(merged) == len(pieces) and (any(flags) == any(merged))
         assert all(hi - lo >= min(n, int(0.01 * SR)) for lo, hi in pieces) or len(pieces) == 1
+
+
+@pytest.mark.gpu
+def test_product_local_valley_refinement_matches_oracle_on_random_cut_lists(hip_ctx):
+    """`_refine_boundaries_local_valley` (ac_local_valley) == oracle refine_local_valley on 20 random cut lists of the seed-11 and
+    seed-12 policy vocals, cuts within one search radius of either end included, at two minimum gaps."""
+    from audio_cut_amd.core.seamless_splitter import SeamlessSplitter
+    from oracle.config import get_config as oget
+    lcl = oget("quality_control.local_boundary_refine", {})
+    radius = max(1, int(float(lcl.get("search_radius_ms", 200)) / 1000.0 * SR))
+    sp = SeamlessSplitter.__new__(SeamlessSplitter)
+    sp.sample_rate = SR
+    sp._hip = hip_ctx
+    sp._last_guard_adjustments_raw = []
+    sp._last_suppressed_cut_points = []
+    rng = np.random.default_rng(99)
+    for seed in (11, 12):
+        voc = policy_case(seed)[0]
+        n = len(voc)
+        dev = hip_ctx.to_device(voc)
+        for case in range(10):
+            k = int(rng.integers(1, 12))
+            inner = rng.integers(0, n + 1, size=k).tolist()
+            inner += [int(rng.integers(0, radius)), int(rng.integers(n - radius, n + 1))][: 1 + case % 2 + (case % 3 == 0)]
+            cuts = sorted(set([0, n] + [int(c) for c in inner]))
+            gap = (0.2, 1.2)[case % 2]
+            got = sp._refine_boundaries_local_valley(cuts, voc, lcl, min_gap_s=gap, vocal_dev=dev)
+            assert got == OL.refine_local_valley(cuts, voc, SR, lcl, gap), (seed, case, cuts)

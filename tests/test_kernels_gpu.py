@@ -1,4 +1,4 @@
-"""Kernel-level parity: every C-ABI entry point against the oracle on seeded inputs (GPU box only)."""
+"""Kernel-level parity against the oracle on seeded inputs (GPU box only); tests/test_abi_and_host.py:EXPORT_TESTS names the test that calls each C-ABI entry point directly."""
 import numpy as np
 import pytest
 import torch
