@@ -41,6 +41,8 @@ def load() -> C.CDLL:
     _declare(lib)
     if lib.ac_abi_version() != 6:
         raise NativeError("libaudiocut_hip.so ABI version mismatch")
+    if lib.ac_stereo_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so stereo ABI version mismatch")
     _lib = lib
     return lib
 
@@ -103,9 +105,17 @@ SIGNATURES = {
     "ac_host_beat_dp": (C.c_int, [_P, _I64, C.c_double, C.c_double, _P, _P]),
 }
 
+# include/audiocut_hip_stereo.h: the true-stereo extension, exported by the same library and versioned on its own
+STEREO_SIGNATURES = {
+    "ac_stereo_abi_version": (C.c_int, []),
+    "ac_mdx_stft_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I, _P, _P, _P]),
+    "ac_mdx_assemble_ola_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "ac_mdx_chunk_vocal_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+}
+
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -682,6 +692,46 @@ class Context:
         out = torch.empty(int(total), dtype=torch.float32, device=self.device)
         _check(self.lib.ac_mdx_chunk_vocal(self._h, _ptr(wave), _ptr(chunk_len), _ptr(out_offset), _ptr(item_base),
                                            chunk_len.numel(), _ptr(out), _stream()))
+        return out
+
+    # -- MDX23, true stereo (include/audiocut_hip_stereo.h): tracks are planar float32 [2, n] ----------------------------------
+    def _chk_stereo(self, track: torch.Tensor) -> None:
+        if track.dtype != torch.float32 or track.device != self.device or track.dim() != 2 or track.shape[0] != 2:
+            raise NativeError("expected a planar [2, n] float32 tensor on the context's device")
+
+    def mdx_stft_stereo(self, track: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
+                        win_index: torch.Tensor, out: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """`mdx_stft` of a stereo track: channels L.re, L.im, R.re, R.im; `amax` takes the maximum over all four."""
+        self._chk_stereo(track)
+        n_items = chunk_start.numel()
+        if out is None:
+            out = torch.empty((n_items, 4, 256, 3072), dtype=torch.float32, device=self.device)
+        _, pa = self._amax_args(n_items, None, amax, 256, 256)
+        _check(self.lib.ac_mdx_stft_stereo(self._h, _ptr(track), track.shape[1], _ptr(chunk_start), _ptr(chunk_len), _ptr(win_index),
+                                           n_items, _ptr(out), pa, _stream()))
+        return out
+
+    def mdx_assemble_ola_stereo(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base,
+                                stereo_stems: bool = True):
+        """-> (vocal [n], inst [n], vocal_stereo [2, n] | None, inst_stereo [2, n] | None): the network's stem and mix minus it."""
+        self._chk_stereo(track)
+        n = track.shape[1]
+        vocal = torch.empty(n, dtype=torch.float32, device=self.device)
+        inst = torch.empty(n, dtype=torch.float32, device=self.device)
+        vocal_st = torch.empty((2, n), dtype=torch.float32, device=self.device) if stereo_stems else None
+        inst_st = torch.empty((2, n), dtype=torch.float32, device=self.device) if stereo_stems else None
+        _check(self.lib.ac_mdx_assemble_ola_stereo(self._h, _ptr(track), n, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len),
+                                                   _ptr(eff_start), _ptr(eff_end), _ptr(item_base), chunk_start.numel(),
+                                                   _ptr(vocal), _ptr(inst), _ptr(vocal_st), _ptr(inst_st), _stream()))
+        return vocal, inst, vocal_st, inst_st
+
+    def mdx_chunk_vocal_stereo(self, track: torch.Tensor, wave: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
+                               out_offset: torch.Tensor, item_base: torch.Tensor, total: int, mix_minus: bool = False) -> torch.Tensor:
+        self._chk_stereo(track)
+        out = torch.empty(int(total), dtype=torch.float32, device=self.device)
+        _check(self.lib.ac_mdx_chunk_vocal_stereo(self._h, _ptr(track), track.shape[1], _ptr(wave), _ptr(chunk_start), _ptr(chunk_len),
+                                                  _ptr(out_offset), _ptr(item_base), chunk_len.numel(), int(bool(mix_minus)), _ptr(out),
+                                                  _stream()))
         return out
 
     # -- U-Net layers (NCHW float32; `in_amax` / `out_amax`: per-item max |x| of the input / output tensor, include/audiocut_hip.h) --

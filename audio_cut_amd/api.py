@@ -10,6 +10,12 @@ Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix
 `<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all PCM_24 packed on the GPU (`ac_pack_pcm24`).
 Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included; only the lyrics attachment to segments (ASR
 layer) is absent.  `separate_and_segment` returns the manifest like the reference's does.
+
+`audio.channels` (1 or 2, validated like `config_manager.py:353-354`): with 2 the file is loaded as planar (2, N) float32
+(`load_audio_stereo`; a mono file goes to both channels), the network separates true L/R, and every exported WAV has two
+channels.  Detection runs on the channel mean.  A file at another rate is resampled per channel first and detection sees the
+mean of the resampled channels, whereas `channels: 1` takes the mean first and resamples the mono track; the two orders
+round differently, so the same file may give different cut samples with 1 and 2 channels.
 """
 from __future__ import annotations
 
@@ -24,12 +30,8 @@ from . import config as _config
 from .core.seamless_splitter import SeamlessSplitter
 
 
-def load_audio_mono(path: str) -> tuple:
-    """PCM16/24/32 WAV or .npy -> (mono float32 in [-1, 1], sample_rate).  Channel mean like `librosa.load(mono=True)`."""
-    p = Path(path)
-    if p.suffix.lower() == ".npy":
-        arr = np.load(p)
-        return (np.mean(arr, axis=0) if arr.ndim == 2 else arr).astype(np.float32), 44100
+def _read_wav(p: Path) -> tuple:
+    """PCM16/24/32 WAV -> (float32 [frames, channels] in [-1, 1], sample_rate)."""
     with wave.open(str(p), "rb") as w:
         sr, ch, width, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
         raw = w.readframes(n)
@@ -44,8 +46,45 @@ def load_audio_mono(path: str) -> tuple:
         data = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
     else:
         raise ValueError(f"unsupported WAV sample width {width}")
-    data = data.reshape(-1, ch)
+    return data.reshape(-1, ch), sr
+
+
+def load_audio_mono(path: str) -> tuple:
+    """PCM16/24/32 WAV or .npy -> (mono float32 in [-1, 1], sample_rate).  Channel mean like `librosa.load(mono=True)`."""
+    p = Path(path)
+    if p.suffix.lower() == ".npy":
+        arr = np.load(p)
+        return (np.mean(arr, axis=0) if arr.ndim == 2 else arr).astype(np.float32), 44100
+    data, sr = _read_wav(p)
+    ch = data.shape[1]
     return np.mean(data, axis=1).astype(np.float32) if ch > 1 else data[:, 0].copy(), sr
+
+
+def load_audio_stereo(path: str) -> tuple:
+    """PCM16/24/32 WAV or .npy -> (planar float32 (2, N) in [-1, 1], sample_rate) for `audio.channels: 2`.  A mono file (a 1-D
+    or (1, N) array, a 1-channel WAV) is duplicated to both channels; more than two channels is refused.  `.npy` arrays are
+    (channels, N) like the mono loader reads them, at 44100 Hz."""
+    p = Path(path)
+    if p.suffix.lower() == ".npy":
+        arr, sr = np.asarray(np.load(p), dtype=np.float32), 44100
+        arr = arr[None, :] if arr.ndim == 1 else arr
+        if arr.ndim != 2:
+            raise ValueError(f"{p}: expected a 1-D or (channels, N) array, got shape {arr.shape}")
+    else:
+        data, sr = _read_wav(p)
+        arr = data.T
+    if arr.shape[0] == 1:
+        arr = np.concatenate([arr, arr], axis=0)
+    if arr.shape[0] != 2:
+        raise ValueError(f"{p}: {arr.shape[0]} channels; audio.channels: 2 takes mono or stereo input")
+    return np.ascontiguousarray(arr, dtype=np.float32), sr
+
+
+def _check_channels(value: Any) -> int:
+    """`config_manager.py:353-354`: audio.channels must be 1 or 2."""
+    if value not in (1, 2):
+        raise ValueError(f"unsupported audio.channels: {value!r} (1 or 2)")
+    return int(value)
 
 
 def _sha256(path: Path) -> str:
@@ -114,8 +153,8 @@ def separate_and_segment(*, input_uri: str, export_dir: str, mode: Optional[str]
         _config.set_runtime_config(overrides)
         layout_cfg = dict(_config.get_config("segment_layout", {}) or {})
         sr = int(_config.get_config("audio.sample_rate", 44100))
-        channels = int(_config.get_config("audio.channels", 1))
-        result = _split_and_export(in_path, out_dir, resolved_mode, export_types, sr, device)
+        channels = _check_channels(_config.get_config("audio.channels", 1))
+        result = _split_and_export(in_path, out_dir, resolved_mode, export_types, sr, device, channels)
     finally:
         _config.restore(saved)
     global _LAST_RESULT
@@ -138,19 +177,27 @@ def last_result() -> Optional[Dict[str, Any]]:
 
 
 def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Optional[Sequence[str]], sr: int,
-                      device: Optional[str]) -> Dict[str, Any]:
+                      device: Optional[str], channels: int = 1) -> Dict[str, Any]:
     """The reference's `split_audio_seamlessly` for the modes built here (`seamless_splitter.py:171-253,270-760`): load,
-    split, export, and the result dict `_build_manifest` reads."""
+    split, export, and the result dict `_build_manifest` reads.  `channels == 2`: the planar stereo track is split (true-stereo
+    separation, detection on its channel mean) and every file is written with both channels."""
     import time
     from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter
     t_start = time.time()
-    audio, file_sr = load_audio_mono(str(in_path))
     splitter = SeamlessSplitter(sample_rate=sr, device=device)
     hip = splitter._context()
     audio_dev = None
-    if file_sr != sr:
-        audio_dev = hip.resample_poly(hip.to_device(audio), sr, file_sr)     # e.g. 48 kHz -> 44.1 kHz = up 147 / down 160
-        audio = audio_dev.cpu().numpy()
+    if channels == 2:
+        audio, file_sr = load_audio_stereo(str(in_path))
+        if file_sr != sr:                     # each channel on its own; detection then reads the mean of the resampled channels
+            import torch
+            audio_dev = torch.stack([hip.resample_poly(hip.to_device(audio[c]), sr, file_sr) for c in range(2)])
+            audio = audio_dev.cpu().numpy()
+    else:
+        audio, file_sr = load_audio_mono(str(in_path))
+        if file_sr != sr:
+            audio_dev = hip.resample_poly(hip.to_device(audio), sr, file_sr)     # e.g. 48 kHz -> 44.1 kHz = up 147 / down 160
+            audio = audio_dev.cpu().numpy()
     res = splitter.split_track(audio, mode=mode, audio_dev=audio_dev)
     single = bool(res.get("single_segment"))            # `_create_single_segment_result`: only the mix, no duration tag
     plan = _normalize_export_plan(export_types) if (export_types or not single) else ["mix_segments"]
@@ -162,23 +209,26 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     exp = ExportResult()
     exporter = SegmentExporter(sr)
     state = res.get("device_state") or {}
+    # the tracks written: mono, or with two channels the stereo mix and stems ([2, N], host and device)
+    st = "_stereo" if channels == 2 else ""
+    mix_dev = state.get("mix_stereo", audio_dev) if channels == 2 else state.get("mix", audio_dev)
     if "mix_segments" in plan:
-        mix_pk = PackedTrack(audio, sr, hip=hip, dev=state.get("mix", audio_dev))
+        mix_pk = PackedTrack(audio, sr, hip=hip, dev=mix_dev)
         exp.mix_segment_files = exporter.export_spans(mix_pk, spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap)
         exp.saved_files += exp.mix_segment_files
-    vocal = res.get("vocal_track")
-    voc_pk = PackedTrack(vocal, sr, hip=hip, dev=state.get("vocal")) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
+    vocal = res.get("vocal_track" + st)
+    voc_pk = PackedTrack(vocal, sr, hip=hip, dev=state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
     if "vocal_segments" in plan and voc_pk is not None:
         exp.vocal_segment_files = exporter.export_spans(voc_pk, spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
                                                         file_suffix="_vocal", duration_map=dmap)
         exp.saved_files += exp.vocal_segment_files
     if "full_vocal" in plan and voc_pk is not None:
-        exp.full_vocal_file = exporter.export_full_track(voc_pk, out_dir / f"{in_path.stem}_{mode}_vocal_full_{len(vocal) / float(sr):.1f}")
+        exp.full_vocal_file = exporter.export_full_track(voc_pk, out_dir / f"{in_path.stem}_{mode}_vocal_full_{np.shape(vocal)[-1] / float(sr):.1f}")
         exp.saved_files.append(exp.full_vocal_file)
-    inst = res.get("instrumental_track")
+    inst = res.get("instrumental_track" + st)
     if "full_instrumental" in plan and inst is not None:
-        inst_pk = PackedTrack(inst, sr, hip=hip, dev=state.get("instrumental"))
-        exp.full_instrumental_file = exporter.export_full_track(inst_pk, out_dir / f"{in_path.stem}_{mode}_instrumental_{len(inst) / float(sr):.1f}")
+        inst_pk = PackedTrack(inst, sr, hip=hip, dev=state.get("instrumental" + st))
+        exp.full_instrumental_file = exporter.export_full_track(inst_pk, out_dir / f"{in_path.stem}_{mode}_instrumental_{np.shape(inst)[-1] / float(sr):.1f}")
         exp.saved_files.append(exp.full_instrumental_file)
     out: Dict[str, Any] = {
         "success": True, "mode": mode, "method": f"pure_vocal_split_{mode}", "input_file": str(in_path), "output_dir": str(out_dir),
@@ -355,4 +405,4 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
     return manifest
 
 
-__all__ = ["separate_and_segment", "load_audio_mono", "last_result"]
+__all__ = ["separate_and_segment", "load_audio_mono", "load_audio_stereo", "last_result"]

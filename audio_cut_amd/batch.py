@@ -55,7 +55,8 @@ class TrackPipeline:
     (VAD bookkeeping, pause detection, guard, boundary policy: ~20 ms of small kernels and synchronisation round trips) on its own
     stream while the next track's U-Net - already waiting in the queue - runs: the GPU never idles between two tracks, and two U-Nets
     never run at once (that only slows both: the package power is the shared budget).  Tracks stay independent: no state is shared
-    between workers, results come back in submission order and are bit-identical to one-at-a-time processing."""
+    between workers, results come back in submission order and are bit-identical to one-at-a-time processing.
+    Mono only: `split_track` refuses a stereo (2, N) track together with the pipeline's gate or U-Net stream (ValueError)."""
 
     def __init__(self, splitters: Sequence, device) -> None:
         import threading

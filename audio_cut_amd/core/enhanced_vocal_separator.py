@@ -17,6 +17,9 @@ the host: pin/copy, `infer_chunk`, VAD, effective-region `+=` into three N-sampl
 
 Failure contract (`:173-188`): the reference falls back to a CPU backend unless `strict_gpu`.  This
 build has no CPU backend by design, so a failure is recorded in `gpu_pipeline_failures` and re-raised.
+
+A planar stereo (2, N) track is separated on true L/R (include/audiocut_hip_stereo.h); everything after the
+separation reads its mono mix (L + R) * 0.5, and the [2, N] stems come back beside the mono ones.
 """
 from __future__ import annotations
 
@@ -52,6 +55,10 @@ class SeparationResult:
     pipeline_used: bool = False
     # extension (not in the reference dataclass): stems / mix still resident in HBM for the detector and guard
     device_state: Optional[Dict[str, object]] = None
+    # extension, stereo input only: the mono mix (L + R) * 0.5 everything downstream reads, and the [2, N] stems
+    mono_mix: Optional[np.ndarray] = None
+    vocal_track_stereo: Optional[np.ndarray] = None
+    instrumental_track_stereo: Optional[np.ndarray] = None
 
 
 def compute_vocal_presence_markers(hip: "_native.Context", vocal_dev: torch.Tensor, sr: int) -> Dict:
@@ -126,7 +133,7 @@ class EnhancedVocalSeparator:
 
     def _ensure_pipeline_context(self, audio: np.ndarray, gpu_context: Optional[PipelineContext]) -> PipelineContext:
         cfg = self._pipeline_cfg
-        duration_s = float(len(audio)) / float(self.sample_rate) if self.sample_rate > 0 else 0.0
+        duration_s = float(np.shape(audio)[-1]) / float(self.sample_rate) if self.sample_rate > 0 else 0.0
         if gpu_context and gpu_context.enabled:
             if not gpu_context.plans:
                 gpu_context.plans = chunk_schedule(duration_s, chunk_s=cfg.chunk_s, overlap_s=cfg.overlap_s, halo_s=cfg.halo_s)
@@ -141,7 +148,10 @@ class EnhancedVocalSeparator:
     # ------------------------------------------------------------------------------------------
     def separate_for_detection(self, audio: np.ndarray, *, gpu_context: Optional[PipelineContext] = None,
                                audio_dev: Optional[torch.Tensor] = None, separation_gate=None, unet_stream=None) -> SeparationResult:
-        """`audio_dev` (extension): the same mono track already resident in HBM; skips the upload.
+        """`audio` is a mono [N] or a planar stereo [2, N] float32 track.  A stereo track is separated on true L/R; the mono mix
+        (L + R) * 0.5 is formed once on the device, and the feature builder, VAD and stems' consumers see exactly what they see for
+        a mono track of those samples.  The result then carries `mono_mix` and the [2, N] stems (host, and `device_state`).
+        `audio_dev` (extension): the same track already resident in HBM; skips the upload.
         `unet_stream` (extension, `batch.TrackPipeline.unet_stream`): the one stream all workers queue their separations on; the
         gate is then held only while this track's launches are being queued, and the next track's U-Net sits in the queue behind
         this one (no idle GPU between two tracks).
@@ -152,13 +162,15 @@ class EnhancedVocalSeparator:
             # the backend, its network and its scratch are shared by every worker: without the gate two threads interleave one
             # track's STFT / U-Net / iSTFT launches with another's on that one stream
             raise ValueError("unet_stream needs separation_gate (batch.TrackPipeline hands out both)")
+        if np.ndim(audio) == 2 and (separation_gate is not None or unet_stream is not None):
+            raise ValueError("stereo tracks are separated one at a time: batch.TrackPipeline and multi-GPU runs take mono [N] tracks")
         backend = self._primary_backend
         if backend is None:
             raise RuntimeError("separator backend not initialised")
         start = time.time()
         ctx = self._ensure_pipeline_context(audio, gpu_context)
         try:
-            vocal, inst, cache, vad_segments, markers, confidence, state = self._separate_with_pipeline(
+            vocal, inst, cache, vad_segments, markers, confidence, state, stereo_out = self._separate_with_pipeline(
                 audio, backend, ctx, audio_dev, separation_gate, unet_stream)
         except Exception as exc:
             ctx.mark_failure("separation", str(exc))
@@ -167,7 +179,7 @@ class EnhancedVocalSeparator:
         return SeparationResult(
             vocal_track=vocal, instrumental_track=inst, separation_confidence=confidence,
             backend_used=type(backend).__name__, processing_time=time.time() - start, quality_metrics=markers,
-            feature_cache=cache, vad_segments=vad_segments, gpu_meta=meta, pipeline_used=ctx.enabled, device_state=state)
+            feature_cache=cache, vad_segments=vad_segments, gpu_meta=meta, pipeline_used=ctx.enabled, device_state=state, **stereo_out)
 
     def _separate_with_pipeline(self, audio: np.ndarray, backend: IVocalSeparatorBackend, gpu_context: PipelineContext,
                                 audio_dev: Optional[torch.Tensor] = None, separation_gate=None, unet_stream=None):
@@ -176,17 +188,24 @@ class EnhancedVocalSeparator:
         sr = self.sample_rate
         hip = backend.hip
         plans = gpu_context.plans
-        total = len(audio)
+        stereo = np.ndim(audio) == 2
+        if stereo and np.shape(audio)[0] != 2:
+            raise ValueError("a stereo track is a planar (2, N) array")
+        total = int(np.shape(audio)[-1])
         timings: Dict[str, float] = {}
         # per-call metrics only: under batch.TrackPipeline another track shares this backend and this device, so nothing
         # backend- or device-global is reset here (the stage timings of THIS call come back through `timings`)
         t0 = time.perf_counter()
         if audio_dev is not None:
-            if audio_dev.numel() != total or audio_dev.dtype != torch.float32:
+            if stereo and (tuple(audio_dev.shape) != (2, total) or not audio_dev.is_contiguous()):
+                raise ValueError("audio_dev must be the contiguous [2, N] device copy of the stereo `audio`")
+            if audio_dev.numel() != np.size(audio) or audio_dev.dtype != torch.float32:
                 raise ValueError("audio_dev must be the float32 device copy of `audio`")
-            mix_dev = audio_dev
+            track_dev = audio_dev
         else:
-            mix_dev = hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+            track_dev = hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+        # the mono mix of a stereo track, formed once: (L + R) * 0.5 in float32 - np.mean(x, axis=0) bit for bit
+        mix_dev = torch.add(track_dev[0], track_dev[1]).mul_(0.5) if stereo else track_dev
         torch.cuda.current_stream(hip.device).synchronize()     # this stream only: another track may be in flight on the device
         h2d_ms = (time.perf_counter() - t0) * 1000.0
 
@@ -203,18 +222,26 @@ class EnhancedVocalSeparator:
                 gate_held.pop()
                 separation_gate.release()
         try:
-            return self._separate_gated(audio, backend, gpu_context, mix_dev, plans, timings, h2d_ms, take_gate, drop_gate, unet_stream)
+            return self._separate_gated(audio, backend, gpu_context, track_dev, mix_dev, plans, timings, h2d_ms, take_gate, drop_gate,
+                                        unet_stream)
         finally:
             drop_gate()
 
-    def _separate_gated(self, audio, backend, gpu_context, mix_dev, plans, timings, h2d_ms, take_gate, drop_gate, unet_stream=None):
+    def _separate_gated(self, audio, backend, gpu_context, track_dev, mix_dev, plans, timings, h2d_ms, take_gate, drop_gate,
+                        unet_stream=None):
         sr = self.sample_rate
         hip = backend.hip
-        total = len(audio)
+        stereo = track_dev.dim() == 2
+        total = int(track_dev.shape[-1])
         mix_ready = torch.cuda.Event()
         mix_ready.record()
-        sep = backend.separate_track(mix_dev, sr, plans, timings, defer_sync=True, before_launch=take_gate, unet_stream=unet_stream,
+        sep = backend.separate_track(track_dev, sr, plans, timings, defer_sync=True, before_launch=take_gate, unet_stream=unet_stream,
                                      after_launch=drop_gate if unet_stream is not None else None)
+        if stereo:
+            # the host copy of the mono mix for the host-side consumers, computed while the GPU runs the separation (the same
+            # float32 arithmetic as mix_dev)
+            audio = np.add(audio[0], audio[1], dtype=np.float32)
+            audio *= np.float32(0.5)
         sep_done = torch.cuda.Event()
         sep_done.record()
         # the track-global kernels whose parameters no host decision touches (analysis/prefetch.py): the mix's on the side stream
@@ -247,6 +274,12 @@ class EnhancedVocalSeparator:
             inst_h = torch.empty(sep.instrumental.shape, dtype=torch.float32, pin_memory=True)
             vocal_h.copy_(sep.vocal, non_blocking=True)
             inst_h.copy_(sep.instrumental, non_blocking=True)
+            if stereo:
+                sep.vocal_stereo.record_stream(side); sep.instrumental_stereo.record_stream(side)
+                vocal_st_h = torch.empty(sep.vocal_stereo.shape, dtype=torch.float32, pin_memory=True)
+                inst_st_h = torch.empty(sep.instrumental_stereo.shape, dtype=torch.float32, pin_memory=True)
+                vocal_st_h.copy_(sep.vocal_stereo, non_blocking=True)
+                inst_st_h.copy_(sep.instrumental_stereo, non_blocking=True)
             stems_on_host = torch.cuda.Event()
             stems_on_host.record()
 
@@ -292,7 +325,12 @@ class EnhancedVocalSeparator:
         gm["mdx23_output_type"] = backend.get_output_type()
         gm["gpu_pipeline_stage_ms"] = dict(timings)
         state = {"hip": hip, "mix": mix_dev, "vocal": sep.vocal, "instrumental": sep.instrumental, "timings": timings}
-        return vocal, inst, cache, vad_segments, markers, confidence, state
+        stereo_out: Dict[str, object] = {}
+        if stereo:
+            state.update({"mix_stereo": track_dev, "vocal_stereo": sep.vocal_stereo, "instrumental_stereo": sep.instrumental_stereo})
+            stereo_out = {"mono_mix": audio, "vocal_track_stereo": vocal_st_h.numpy(),
+                          "instrumental_track_stereo": inst_st_h.numpy() if has_inst else None}
+        return vocal, inst, cache, vad_segments, markers, confidence, state, stereo_out
 
     def _side_stream(self, hip) -> "torch.cuda.Stream":
         """A second HIP stream (high priority) for the mix-only feature path that overlaps the U-Net."""

@@ -78,16 +78,22 @@ class SeamlessSplitter:
         stream): with both, this track's separation is queued on that stream under the lock and the lock is released as soon as it is
         queued - the stream itself keeps the U-Nets of consecutive tracks one after the other, and the next one waits in the queue
         behind the running one.  With the gate alone (round 2's scheme) the lock is held until this track's U-Net has left the GPU and
-        released before the host-bound tail."""
+        released before the host-bound tail.
+        A planar stereo (2, N) track (and a [2, N] `audio_dev`) is separated on true L/R; detection, guards and boundaries run on its
+        mono mix (L + R) * 0.5 exactly as on a mono track of those samples, and the result adds `vocal_track_stereo` /
+        `instrumental_track_stereo` ([2, N]) and `mono_mix`.  Stereo tracks are not taken with a gate or U-Net stream."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
         sr = self.sample_rate
-        if original_audio is None or len(original_audio) == 0:
+        if original_audio is None or len(original_audio) == 0 or np.shape(original_audio)[-1] == 0:
             raise ValueError("split_track needs a non-empty mono track")
+        stereo = np.ndim(original_audio) == 2
         t0 = time.perf_counter()
         sep: SeparationResult = self.separator.separate_for_detection(original_audio, gpu_context=None, audio_dev=audio_dev,
                                                                      separation_gate=separation_gate, unet_stream=unet_stream)
         t_sep = time.perf_counter() - t0
+        if stereo:
+            original_audio = sep.mono_mix          # everything below reads the mono mix
         state = sep.device_state or {}
         vocal_track = sep.vocal_track
         cache: Optional[TrackFeatureCache] = sep.feature_cache
@@ -102,6 +108,9 @@ class SeamlessSplitter:
                         "separation_confidence": sep.separation_confidence, "backend_used": sep.backend_used,
                         "vad_segments": sep.vad_segments, "feature_cache": cache,
                         "vocal_track": vocal_track, "instrumental_track": sep.instrumental_track, "device_state": state}
+        if stereo:
+            result.update({"vocal_track_stereo": sep.vocal_track_stereo, "instrumental_track_stereo": sep.instrumental_track_stereo,
+                           "mono_mix": sep.mono_mix})
         if is_vpbd:
             # reference `:362-408`.  The smart_cut intent / AutoProfile runtime overrides applied at `:349` are
             # product configuration policy (out of scope): VPBD runs on the base configuration.

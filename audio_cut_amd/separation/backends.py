@@ -16,7 +16,9 @@ describe_input / fallback_to_cpu` discovered with `getattr`, `:134-135,183-208,2
 
 `infer_chunk` keeps the reference's per-chunk contract (mono float32 in, mono vocal/instrumental of
 the same length out) on top of the same kernels; `separate_track` is the batched fast path the
-separator uses.  There is no CPU execution provider to fall back to: `fallback_to_cpu()` raises.
+separator uses.  A planar [2, N] track takes the true-stereo kernels (include/audiocut_hip_stereo.h):
+the network sees L and R as they are, the mono stems are the channel means of the stereo ones, and
+the stereo stems come back beside them.  There is no CPU execution provider to fall back to: `fallback_to_cpu()` raises.
 """
 from __future__ import annotations
 
@@ -77,6 +79,8 @@ class TrackSeparation:
     chunk_ranges: List[Tuple[int, int, int, int]]   # (chunk_start, chunk_end, eff_start, eff_end)
     n_items: int
     finish: Optional[object] = None   # callable: waits for the queued work and fills the stage timings (separate_track(defer_sync=True))
+    vocal_stereo: Optional[torch.Tensor] = None          # [2, N] f32 for a stereo track, else None
+    instrumental_stereo: Optional[torch.Tensor] = None   # [2, N] f32 for a stereo track, else None
 
 
 def items_per_chunk(chunk_len: int, align_hop: int) -> int:
@@ -189,10 +193,16 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         `unet_stream`: queue the whole separation on THAT stream instead of the current one (the current stream waits for its
         end); `batch.TrackPipeline` gives every worker the same one, so the separations of consecutive tracks are ordered by
         the stream itself and the next one can be queued while this one still runs - `after_launch` is then called as soon as
-        everything is queued (the pipeline's gate only has to keep two tracks' launches from interleaving)."""
+        everything is queued (the pipeline's gate only has to keep two tracks' launches from interleaving).
+        `track_dev` is a mono [N] or a planar stereo [2, N] float32 track; a stereo one also fills `vocal_stereo` / `instrumental_stereo`."""
         hip = self.hip
         net = self.net
-        n = int(track_dev.numel())
+        if track_dev.dim() == 2:
+            if track_dev.shape[0] != 2 or not track_dev.is_contiguous():
+                raise ValueError("a stereo track is a contiguous planar [2, N] tensor")
+        elif track_dev.dim() != 1:
+            raise ValueError("track_dev must be [N] (mono) or [2, N] (stereo)")
+        n = int(track_dev.shape[-1])
         ranges: List[Tuple[int, int, int, int]] = []
         for p in plans:        # enhanced_vocal_separator.py:367-368,423-425
             cs = max(0, int(round(p.start_s * sr)))
@@ -236,13 +246,14 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             if unet_stream is not None:
                 queued = torch.cuda.Event()
                 queued.record()
-        wave, vocal, inst, chunk_vocal, events = sep_out
+        wave, vocal, inst, chunk_vocal, vocal_st, inst_st, events = sep_out
         if unet_stream is not None:
             if after_launch is not None:
                 after_launch()
             caller_stream.wait_event(queued)
-            for t in (wave, vocal, inst, chunk_vocal):
-                t.record_stream(caller_stream)
+            for t in (wave, vocal, inst, chunk_vocal, vocal_st, inst_st):
+                if t is not None:
+                    t.record_stream(caller_stream)
         n_ranges = len(ranges)
 
         def finish() -> None:      # one synchronisation for the whole track, after everything has been queued
@@ -260,13 +271,15 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         if not defer_sync:
             finish()
         return TrackSeparation(vocal, inst, chunk_vocal, [int(o) for o in offsets[:-1]], ranges, n_items,
-                               finish if defer_sync else None)
+                               finish if defer_sync else None, vocal_st, inst_st)
 
     def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables):
         """Queues STFT -> U-Net -> iSTFT of every sub-batch and the stem assembly on the CURRENT stream; no host synchronisation."""
         hip = self.hip
         net = self.net
         d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets = tables
+        stereo = track_dev.dim() == 2
+        stft = hip.mdx_stft_stereo if stereo else hip.mdx_stft
         wave = torch.empty((n_items, 2, ITEM_LEN), dtype=torch.float32, device=hip.device)
         events: List[List[torch.cuda.Event]] = []     # per sub-batch: [before stft, before net, before istft, after istft]
         for a in range(0, n_items, step):
@@ -274,7 +287,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
             if ev: ev[0].record()
             amax = torch.zeros((b - a, 256), dtype=torch.float32, device=hip.device)  # max |spec| per item and frame: the first conv's activation scale
-            spec = hip.mdx_stft(track_dev, d_cs[a:b].contiguous(), d_cl[a:b].contiguous(), d_wi[a:b].contiguous(), amax=amax)
+            spec = stft(track_dev, d_cs[a:b].contiguous(), d_cl[a:b].contiguous(), d_wi[a:b].contiguous(), amax=amax)
             if ev: ev[1].record()
             out = net.forward_tf(spec, amax)
             del spec
@@ -284,6 +297,17 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             if ev:
                 ev[3].record()
                 events.append(ev)
+        if stereo:
+            # the mono stems are the channel means of the stereo ones (mdx_assemble's order); the network's stem and mix minus
+            # it swap for an instrumental-type model exactly like the mono ones, and the VAD input becomes mix minus the stem
+            vocal_like, other, vocal_like_st, other_st = hip.mdx_assemble_ola_stereo(track_dev, wave, d_chunk_start, d_chunk_len,
+                                                                                     d_es, d_ee, d_base)
+            vocal_type = self.get_output_type() == "vocal"
+            chunk_vocal = hip.mdx_chunk_vocal_stereo(track_dev, wave, d_chunk_start, d_chunk_len, d_offsets, d_base, int(offsets[-1]),
+                                                     mix_minus=not vocal_type)
+            if vocal_type:
+                return wave, vocal_like, other, chunk_vocal, vocal_like_st, other_st, events
+            return wave, other, vocal_like, chunk_vocal, other_st, vocal_like_st, events
         vocal_like, other = hip.mdx_assemble_ola(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
         chunk_vocal = hip.mdx_chunk_vocal(wave, d_chunk_len, d_offsets, d_base, int(offsets[-1]))
         if self.get_output_type() == "vocal":
@@ -293,19 +317,17 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             vocal, inst = other, vocal_like
             chunk_mix = torch.cat([track_dev[cs:ce] for cs, ce, _, _ in ranges])
             chunk_vocal = chunk_mix - chunk_vocal
-        return wave, vocal, inst, chunk_vocal, events
+        return wave, vocal, inst, chunk_vocal, None, None, events
 
     # -- reference-shaped per-chunk call ----------------------------------------------------------
     def infer_chunk(self, mix_chunk: np.ndarray, **kwargs) -> SeparationOutputs:
-        """backends.py:299-406 for one chunk (mono, or 2-D with identical rows as the reference feeds)."""
+        """backends.py:299-406 for one chunk: mono, 2-D with identical rows (the mono path), or a true-stereo (2, n) chunk whose
+        rows go through the network as they are; the outputs are the channel means either way."""
         if self._net is None:
             raise RuntimeError("MDX23HipBackend not initialised: call load_model()")
         chunk = np.asarray(mix_chunk, dtype=np.float32)
         if chunk.ndim == 2:
-            if chunk.shape[0] == 2 and not np.array_equal(chunk[0], chunk[1]):
-                raise NotImplementedError("true-stereo chunks: the hot path feeds mono duplicated to 2 channels "
-                                          "(backends.py:269-270); only that case is built")
-            chunk = chunk[0]
+            chunk = chunk if (chunk.shape[0] == 2 and not np.array_equal(chunk[0], chunk[1])) else chunk[0]
         elif chunk.ndim != 1:
             raise ValueError("mix_chunk shape invalid")
         hip = self.hip
@@ -313,7 +335,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         dev = hip.to_device(np.ascontiguousarray(chunk))
         torch.cuda.synchronize(hip.device)
         self._perf["h2d_ms"] += (time.perf_counter() - t0) * 1000.0
-        n = chunk.shape[0]
+        n = chunk.shape[-1]
         plan = ChunkPlan(index=0, start_s=0.0, end_s=n / float(self._sr), halo_left_s=0.0, halo_right_s=0.0)
         sep = self.separate_track(dev, self._sr, [plan])
         t1 = time.perf_counter()

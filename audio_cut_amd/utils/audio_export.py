@@ -6,6 +6,8 @@ The float -> integer conversion runs on the GPU (`ac_pack_pcm24`) on the whole r
 clipping conversion - python-soundfile sets SFC_SET_CLIPPING on every file, so `soundfile.write` goes through pcm.c
 `f2let_clip_array`: `lrintf(x * 2^31) >> 8`, saturating at 0x7FFFFF / 0x800000 (`>> 16` for PCM_16); segment files are byte slices of that buffer behind a 44-byte RIFF header.  MP3 needs
 pydub + FFmpeg in the reference (`:114-135`) and is refused here.
+Stereo tracks are planar (2, N) arrays (the reference writes `(channels, samples)` arrays as multichannel files, `:93-106`): they
+are interleaved frame by frame ([N, 2], on the device before the same packing kernel) and the header carries two channels.
 """
 from __future__ import annotations
 
@@ -67,25 +69,41 @@ def pcm_bytes_host(audio: np.ndarray, subtype: str) -> Tuple[np.ndarray, int]:
     return out.reshape(-1), 3
 
 
+def _channels_of(audio) -> int:
+    """1 for a mono [N] track, 2 for a planar stereo (2, N) one."""
+    nd = len(audio.shape)
+    if nd == 1:
+        return 1
+    if nd == 2 and audio.shape[0] == 2:
+        return 2
+    raise ValueError(f"this build exports mono [N] or stereo (2, N) tracks, got shape {tuple(audio.shape)}")
+
+
 class PackedTrack:
-    """A whole mono track converted once (on the GPU when a context and device tensor are given); slices are cheap."""
+    """A whole mono [N] or planar stereo (2, N) track converted once (on the GPU when a context and device tensor are given);
+    slices are cheap.  Stereo frames are interleaved (L, R) like every multichannel WAV."""
 
     def __init__(self, audio: np.ndarray, sample_rate: int, subtype: str = "PCM_24", *, hip=None, dev=None) -> None:
         self.sample_rate = int(sample_rate)
         self.subtype = subtype
-        self.n = int(len(audio))
+        self.channels = _channels_of(np.asarray(audio) if dev is None else dev)
+        self.n = int(np.shape(audio)[-1])
         if subtype == "PCM_24" and hip is not None and self.n > 0:
             d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+            if self.channels == 2:
+                d = d.t().contiguous().reshape(-1)          # [N, 2]: frame-interleaved, then the mono packing over 2N samples
             self.bytes, self.width = hip.pack_pcm24(d), 3
         else:
-            self.bytes, self.width = pcm_bytes_host(audio, subtype)
+            x = np.asarray(audio)
+            self.bytes, self.width = pcm_bytes_host(x.T if self.channels == 2 else x, subtype)
 
     def write(self, path: Path, start: int = 0, end: Optional[int] = None) -> Path:
         end = self.n if end is None else end
         start = max(0, min(int(start), self.n)); end = max(start, min(int(end), self.n))
+        frame = self.width * self.channels
         with open(path, "wb") as fh:
-            fh.write(wav_header(end - start, self.sample_rate, 1, self.width))
-            fh.write(memoryview(self.bytes)[start * self.width: end * self.width])
+            fh.write(wav_header(end - start, self.sample_rate, self.channels, self.width))
+            fh.write(memoryview(self.bytes)[start * frame: end * frame])
         return Path(path)
 
 
@@ -94,8 +112,7 @@ def export_audio(audio: np.ndarray, sample_rate: int, base_path: Path, format_na
     opts = build_export_options(key, options)
     path = _export_path(Path(base_path), key)
     arr = np.asarray(audio)
-    if arr.ndim != 1:
-        raise ValueError("this build exports mono tracks")
+    _channels_of(arr)
     PackedTrack(arr, sample_rate, str(opts.get("subtype", "PCM_24"))).write(path)
     return path
 
