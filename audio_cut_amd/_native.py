@@ -653,18 +653,26 @@ class Context:
                                             _ptr(cut), _ptr(aux), _stream()))
         return cut.cpu().numpy(), aux.cpu().numpy()
 
-    # -- MDX23 ---------------------------------------------------------------------------------------
+    # -- MDX23: a track is mono float32 [n] or planar stereo float32 [2, n] (include/audiocut_hip_stereo.h) ------------------
+    def _chk_track(self, track: torch.Tensor) -> bool:
+        """-> whether `track` is stereo; anything but a mono [n] or a contiguous planar [2, n] float32 tensor raises."""
+        if track.dtype != torch.float32 or track.device != self.device or not track.is_contiguous() \
+                or not (track.dim() == 1 or (track.dim() == 2 and track.shape[0] == 2)):
+            raise NativeError("expected a mono [n] or a contiguous planar [2, n] float32 tensor on the context's device")
+        return track.dim() == 2
+
     def mdx_stft(self, track: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
                  win_index: torch.Tensor, out: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """`amax` [n_items, 256] float32, zeroed by the caller: receives max |spectrogram| per item and frame (the first conv's
-        time-local activation scale)."""
-        self._chk_f32(track)
+        """-> spectrum [n_items, 4 (L.re, L.im, R.re, R.im), 256, 3072]; a mono track fills L and R alike.
+        `amax` [n_items, 256] float32, zeroed by the caller: receives max |spectrogram| per item and frame over all four channels
+        (the first conv's time-local activation scale)."""
+        fn = self.lib.ac_mdx_stft_stereo if self._chk_track(track) else self.lib.ac_mdx_stft
         n_items = chunk_start.numel()
         if out is None:
             out = torch.empty((n_items, 4, 256, 3072), dtype=torch.float32, device=self.device)
         _, pa = self._amax_args(n_items, None, amax, 256, 256)
-        _check(self.lib.ac_mdx_stft(self._h, _ptr(track), track.numel(), _ptr(chunk_start), _ptr(chunk_len), _ptr(win_index),
-                                    n_items, _ptr(out), pa, _stream()))
+        _check(fn(self._h, _ptr(track), track.shape[-1], _ptr(chunk_start), _ptr(chunk_len), _ptr(win_index), n_items, _ptr(out), pa,
+                  _stream()))
         return out
 
     def mdx_istft(self, spec: torch.Tensor) -> torch.Tensor:
@@ -676,62 +684,39 @@ class Context:
         _check(self.lib.ac_mdx_istft(self._h, _ptr(spec), n_items, _ptr(wave), _ptr(scratch), _stream()))
         return wave
 
-    def mdx_assemble_ola(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base):
-        self._chk_f32(track)
-        n = track.numel()
+    def mdx_assemble_ola(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base,
+                         stereo_stems: bool = True):
+        """-> (vocal [n], inst [n], vocal_stereo [2, n] | None, inst_stereo [2, n] | None): the network's stem and the mix minus
+        it; the stereo stems only for a stereo track, and not with `stereo_stems=False`."""
+        stereo = self._chk_track(track)
+        n = track.shape[-1]
         vocal = torch.empty(n, dtype=torch.float32, device=self.device)
         inst = torch.empty(n, dtype=torch.float32, device=self.device)
-        _check(self.lib.ac_mdx_assemble_ola(self._h, _ptr(track), n, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len),
-                                            _ptr(eff_start), _ptr(eff_end), _ptr(item_base), chunk_start.numel(),
-                                            _ptr(vocal), _ptr(inst), _stream()))
-        return vocal, inst
-
-
-    def mdx_chunk_vocal(self, wave: torch.Tensor, chunk_len: torch.Tensor, out_offset: torch.Tensor, item_base: torch.Tensor,
-                        total: int) -> torch.Tensor:
-        out = torch.empty(int(total), dtype=torch.float32, device=self.device)
-        _check(self.lib.ac_mdx_chunk_vocal(self._h, _ptr(wave), _ptr(chunk_len), _ptr(out_offset), _ptr(item_base),
-                                           chunk_len.numel(), _ptr(out), _stream()))
-        return out
-
-    # -- MDX23, true stereo (include/audiocut_hip_stereo.h): tracks are planar float32 [2, n] ----------------------------------
-    def _chk_stereo(self, track: torch.Tensor) -> None:
-        if track.dtype != torch.float32 or track.device != self.device or track.dim() != 2 or track.shape[0] != 2:
-            raise NativeError("expected a planar [2, n] float32 tensor on the context's device")
-
-    def mdx_stft_stereo(self, track: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
-                        win_index: torch.Tensor, out: Optional[torch.Tensor] = None, amax: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """`mdx_stft` of a stereo track: channels L.re, L.im, R.re, R.im; `amax` takes the maximum over all four."""
-        self._chk_stereo(track)
-        n_items = chunk_start.numel()
-        if out is None:
-            out = torch.empty((n_items, 4, 256, 3072), dtype=torch.float32, device=self.device)
-        _, pa = self._amax_args(n_items, None, amax, 256, 256)
-        _check(self.lib.ac_mdx_stft_stereo(self._h, _ptr(track), track.shape[1], _ptr(chunk_start), _ptr(chunk_len), _ptr(win_index),
-                                           n_items, _ptr(out), pa, _stream()))
-        return out
-
-    def mdx_assemble_ola_stereo(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base,
-                                stereo_stems: bool = True):
-        """-> (vocal [n], inst [n], vocal_stereo [2, n] | None, inst_stereo [2, n] | None): the network's stem and mix minus it."""
-        self._chk_stereo(track)
-        n = track.shape[1]
-        vocal = torch.empty(n, dtype=torch.float32, device=self.device)
-        inst = torch.empty(n, dtype=torch.float32, device=self.device)
+        args = (self._h, _ptr(track), n, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len), _ptr(eff_start), _ptr(eff_end),
+                _ptr(item_base), chunk_start.numel(), _ptr(vocal), _ptr(inst))
+        if not stereo:
+            _check(self.lib.ac_mdx_assemble_ola(*args, _stream()))
+            return vocal, inst, None, None
         vocal_st = torch.empty((2, n), dtype=torch.float32, device=self.device) if stereo_stems else None
         inst_st = torch.empty((2, n), dtype=torch.float32, device=self.device) if stereo_stems else None
-        _check(self.lib.ac_mdx_assemble_ola_stereo(self._h, _ptr(track), n, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len),
-                                                   _ptr(eff_start), _ptr(eff_end), _ptr(item_base), chunk_start.numel(),
-                                                   _ptr(vocal), _ptr(inst), _ptr(vocal_st), _ptr(inst_st), _stream()))
+        _check(self.lib.ac_mdx_assemble_ola_stereo(*args, _ptr(vocal_st), _ptr(inst_st), _stream()))
         return vocal, inst, vocal_st, inst_st
 
-    def mdx_chunk_vocal_stereo(self, track: torch.Tensor, wave: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
-                               out_offset: torch.Tensor, item_base: torch.Tensor, total: int, mix_minus: bool = False) -> torch.Tensor:
-        self._chk_stereo(track)
+    def mdx_chunk_vocal(self, track: torch.Tensor, wave: torch.Tensor, chunk_start: torch.Tensor, chunk_len: torch.Tensor,
+                        out_offset: torch.Tensor, item_base: torch.Tensor, total: int, mix_minus: bool = False) -> torch.Tensor:
+        """-> the per-chunk mono vocals, concatenated: (w0 + w1) / 2, or with `mix_minus` (a stereo track only) the mean over the
+        channels of the mix minus the network's stem."""
+        stereo = self._chk_track(track)
+        if mix_minus and not stereo:
+            raise NativeError("mdx_chunk_vocal: mix_minus needs a stereo track")
         out = torch.empty(int(total), dtype=torch.float32, device=self.device)
-        _check(self.lib.ac_mdx_chunk_vocal_stereo(self._h, _ptr(track), track.shape[1], _ptr(wave), _ptr(chunk_start), _ptr(chunk_len),
-                                                  _ptr(out_offset), _ptr(item_base), chunk_len.numel(), int(bool(mix_minus)), _ptr(out),
-                                                  _stream()))
+        if stereo:
+            _check(self.lib.ac_mdx_chunk_vocal_stereo(self._h, _ptr(track), track.shape[1], _ptr(wave), _ptr(chunk_start),
+                                                      _ptr(chunk_len), _ptr(out_offset), _ptr(item_base), chunk_len.numel(),
+                                                      int(bool(mix_minus)), _ptr(out), _stream()))
+        else:
+            _check(self.lib.ac_mdx_chunk_vocal(self._h, _ptr(wave), _ptr(chunk_len), _ptr(out_offset), _ptr(item_base),
+                                               chunk_len.numel(), _ptr(out), _stream()))
         return out
 
     # -- U-Net layers (NCHW float32; `in_amax` / `out_amax`: per-item max |x| of the input / output tensor, include/audiocut_hip.h) --

@@ -100,6 +100,12 @@ __device__ float2* fft3072_f32(float2* a, float2* b, const float2* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// The MDX kernels are templates on the channel count CH, not one body behind a helper: a helper changed the mono kernels' code.
+// STFT: one workgroup per (frame, item) for a mono track, per (frame, item, channel) for a planar [2][n] stereo track
+// (include/audiocut_hip_stereo.h).  Channel c goes to spectrum channels 2c (re) and 2c+1 (im); a mono track goes to both
+// (backends.py:269-270), so a stereo track with L == R gives the mono spectrum bit for bit.  The amax slot of an (item, frame)
+// receives both channels' workgroups of a stereo track; the ordered-bits atomicMax does not depend on their order.
+template <int CH>
 __global__ __launch_bounds__(256) void k_mdx_stft(const float* __restrict__ track, int64_t n,
                                                   const int64_t* __restrict__ chunk_start,
                                                   const int64_t* __restrict__ chunk_len,
@@ -110,71 +116,7 @@ __global__ __launch_bounds__(256) void k_mdx_stft(const float* __restrict__ trac
     __shared__ float2 s_b[MDX_M];
     const int t = blockIdx.x;            // frame
     const int item = blockIdx.y;
-    const int64_t cs = chunk_start[item];
-    const int64_t cl = chunk_len[item];
-    const int64_t woff = (int64_t)win_index[item] * MDX_GEN - MDX_TRIM;   // chunk-local index of item sample 0
-    for (int m = threadIdx.x; m < MDX_M; m += 256) {
-        float v[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int i = 2 * m + h;
-            int jj = t * MDX_HOP - MDX_NFFT / 2 + i;            // index into the (unpadded) item
-            if (jj < 0) jj = -jj;                               // torch.stft(center=True): reflect padding
-            else if (jj >= MDX_ITEM) jj = 2 * (MDX_ITEM - 1) - jj;
-            const int64_t q = woff + jj;                        // chunk-local sample
-            const float s = (q >= 0 && q < cl) ? track[cs + q] : 0.f;
-            v[h] = s * hann[i];
-        }
-        s_a[m] = make_float2(v[0], v[1]);
-    }
-    __syncthreads();
-    const float2* Z = fft3072_f32(s_a, s_b, tw);
-    float* out = spec + (size_t)item * 4 * MDX_T * MDX_F + (size_t)t * MDX_F;
-    const size_t cstride = (size_t)MDX_T * MDX_F;
-    float vmax = 0.f;
-    for (int k = threadIdx.x; k < MDX_F; k += 256) {
-        const float2 zk = Z[k];
-        const float2 zn = Z[(MDX_M - k) % MDX_M];
-        const float2 e = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
-        const float2 o = make_float2(0.5f * (zk.x - zn.x), 0.5f * (zk.y + zn.y));
-        const float2 wo = cmulf(tw[k], o);
-        const float re = e.x + wo.y, im = e.y - wo.x;
-        out[k] = re;                       // L.re
-        out[cstride + k] = im;             // L.im
-        out[2 * cstride + k] = re;         // R.re  (mono input duplicated to both channels, backends.py:269-270)
-        out[3 * cstride + k] = im;         // R.im
-        vmax = fmaxf(vmax, fmaxf(fabsf(re), fabsf(im)));
-    }
-    // max |spectrogram| per (item, frame): the first conv's time-local activation scale (ac_common.h)
-    if (spec_amax) ac_amax_commit(vmax, spec_amax + (size_t)item * MDX_T + t);
-}
-
-extern "C" int ac_mdx_stft(ac_ctx* ctx, const float* track, int64_t n, const int64_t* chunk_start, const int64_t* chunk_len,
-                           const int32_t* win_index, int n_items, float* spec_out, float* spec_amax, void* stream) {
-    AC_REQUIRE(ctx && track && chunk_start && chunk_len && win_index && spec_out, "null pointer");
-    AC_REQUIRE(n > 0 && n_items > 0 && n_items <= 65535, "n_items must be in [1, 65535]");
-    hipLaunchKernelGGL(k_mdx_stft, dim3(MDX_T, n_items), dim3(256), 0, (hipStream_t)stream, track, n, chunk_start, chunk_len,
-                       win_index, ctx->tw6144, ctx->hann6144, spec_out, spec_amax);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-// True stereo (include/audiocut_hip_stereo.h): one workgroup per (frame, item, channel).  Channel c of the planar [2][n] track
-// goes to spectrum channels 2c (re) and 2c+1 (im) through exactly k_mdx_stft's per-channel arithmetic - the same windowing,
-// fft3072_f32, untangle - so a track with L == R gives k_mdx_stft's spectrum bit for bit.  (The body is restated rather than
-// shared through a helper: routing k_mdx_stft through one changes its register allocation, and its code object stays as it is.)
-// The amax slot of an (item, frame) receives both channels' workgroups; the ordered-bits atomicMax does not depend on their order.
-__global__ __launch_bounds__(256) void k_mdx_stft_stereo(const float* __restrict__ track, int64_t n,
-                                                         const int64_t* __restrict__ chunk_start,
-                                                         const int64_t* __restrict__ chunk_len,
-                                                         const int32_t* __restrict__ win_index,
-                                                         const float2* __restrict__ tw, const float* __restrict__ hann,
-                                                         float* __restrict__ spec, float* __restrict__ spec_amax) {
-    __shared__ float2 s_a[MDX_M];
-    __shared__ float2 s_b[MDX_M];
-    const int t = blockIdx.x;            // frame
-    const int item = blockIdx.y;
-    const int ch = blockIdx.z;
+    const int ch = CH == 2 ? (int)blockIdx.z : 0;
     const float* x = track + (size_t)ch * n;
     const int64_t cs = chunk_start[item];
     const int64_t cl = chunk_len[item];
@@ -207,21 +149,35 @@ __global__ __launch_bounds__(256) void k_mdx_stft_stereo(const float* __restrict
         const float re = e.x + wo.y, im = e.y - wo.x;
         out[k] = re;                       // L.re / R.re
         out[cstride + k] = im;             // L.im / R.im
+        if (CH == 1) {
+            out[2 * cstride + k] = re;     // R.re
+            out[3 * cstride + k] = im;     // R.im
+        }
         vmax = fmaxf(vmax, fmaxf(fabsf(re), fabsf(im)));
     }
+    // max |spectrogram| per (item, frame): the first conv's time-local activation scale (ac_common.h)
     if (spec_amax) ac_amax_commit(vmax, spec_amax + (size_t)item * MDX_T + t);
+}
+
+extern "C" int ac_mdx_stft(ac_ctx* ctx, const float* track, int64_t n, const int64_t* chunk_start, const int64_t* chunk_len,
+                           const int32_t* win_index, int n_items, float* spec_out, float* spec_amax, void* stream) {
+    AC_REQUIRE(ctx && track && chunk_start && chunk_len && win_index && spec_out, "null pointer");
+    AC_REQUIRE(n > 0 && n_items > 0 && n_items <= 65535, "n_items must be in [1, 65535]");
+    hipLaunchKernelGGL(k_mdx_stft<1>, dim3(MDX_T, n_items), dim3(256), 0, (hipStream_t)stream, track, n, chunk_start, chunk_len,
+                       win_index, ctx->tw6144, ctx->hann6144, spec_out, spec_amax);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
 }
 
 extern "C" int ac_mdx_stft_stereo(ac_ctx* ctx, const float* track, int64_t n, const int64_t* chunk_start, const int64_t* chunk_len,
                                   const int32_t* win_index, int n_items, float* spec_out, float* spec_amax, void* stream) {
     AC_REQUIRE(ctx && track && chunk_start && chunk_len && win_index && spec_out, "null pointer");
     AC_REQUIRE(n > 0 && n_items > 0 && n_items <= 65535, "n_items must be in [1, 65535]");
-    hipLaunchKernelGGL(k_mdx_stft_stereo, dim3(MDX_T, n_items, 2), dim3(256), 0, (hipStream_t)stream, track, n, chunk_start, chunk_len,
+    hipLaunchKernelGGL(k_mdx_stft<2>, dim3(MDX_T, n_items, 2), dim3(256), 0, (hipStream_t)stream, track, n, chunk_start, chunk_len,
                        win_index, ctx->tw6144, ctx->hann6144, spec_out, spec_amax);
     AC_LAUNCH_CHECK();
     return AC_OK;
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // iSTFT stage 1: one workgroup per (item, channel, frame): Hermitian spectrum (top bin zero, imaginary
@@ -289,103 +245,27 @@ extern "C" int ac_mdx_istft(ac_ctx* ctx, const float* spec, int n_items, float* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Stem assembly + uniform overlap-add of the effective regions, as a gather over track samples.
+// Stem assembly + uniform overlap-add of the effective regions, as a gather over track samples.  Per covering chunk, in chunk
+// order, the mono stems are the channel means in mdx_assemble's order, (w0 + w1) * 0.5 and ((m0 - w0) + (m1 - w1)) * 0.5
+// (m0 == m1 for a mono track); a planar [2][n] stereo track also accumulates w_c and m_c - w_c per channel for the stereo stems.
+// Every sum is divided by the same count of covering chunks.
+template <int CH>
 __global__ __launch_bounds__(256) void k_mdx_assemble_ola(const float* __restrict__ track, int64_t n, const float* __restrict__ wave,
                                                           const int64_t* __restrict__ chunk_start,
                                                           const int64_t* __restrict__ chunk_len,
                                                           const int64_t* __restrict__ eff_start,
                                                           const int64_t* __restrict__ eff_end,
                                                           const int32_t* __restrict__ item_base, int n_chunks,
-                                                          float* __restrict__ vocal_out, float* __restrict__ inst_out) {
+                                                          float* __restrict__ vocal_out, float* __restrict__ inst_out,
+                                                          float* __restrict__ vocal_st_out, float* __restrict__ inst_st_out) {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= n) return;
     // chunks whose effective region contains g form a contiguous index range (both tables ascend)
     int lo = 0, hi = n_chunks;              // first chunk with eff_end > g
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (eff_end[mid] > g) hi = mid; else lo = mid + 1; }
     const int c_lo = lo;
-    const float mix = track[g];
-    float v_acc = 0.f, i_acc = 0.f, w_acc = 0.f;
-    for (int c = c_lo; c < n_chunks && eff_start[c] <= g; ++c) {
-        if (eff_end[c] <= g) continue;
-        const int64_t q = g - chunk_start[c];
-        if (q < 0 || q >= chunk_len[c]) continue;
-        const int item = item_base[c] + (int)(q / MDX_GEN);
-        const int pos = MDX_TRIM + (int)(q % MDX_GEN);
-        const float w0 = wave[((size_t)item * 2 + 0) * MDX_ITEM + pos];
-        const float w1 = wave[((size_t)item * 2 + 1) * MDX_ITEM + pos];
-        const float vocal = (w0 + w1) * 0.5f;                // vocal.mean(axis=0) in float32
-        const float inst = ((mix - w0) + (mix - w1)) * 0.5f; // (mix - vocal).mean(axis=0)
-        v_acc += vocal;
-        i_acc += inst;
-        w_acc += 1.0f;
-    }
-    if (w_acc == 0.f) w_acc = 1.0f;
-    vocal_out[g] = v_acc / w_acc;
-    inst_out[g] = i_acc / w_acc;
-}
-
-extern "C" int ac_mdx_assemble_ola(ac_ctx* ctx, const float* track, int64_t n, const float* wave, const int64_t* chunk_start,
-                                   const int64_t* chunk_len, const int64_t* eff_start, const int64_t* eff_end,
-                                   const int32_t* item_base, int n_chunks, float* vocal_out, float* inst_out, void* stream) {
-    AC_REQUIRE(ctx && track && wave && chunk_start && chunk_len && eff_start && eff_end && item_base && vocal_out && inst_out,
-               "null pointer");
-    AC_REQUIRE(n > 0 && n_chunks > 0, "sizes must be positive");
-    const int64_t blocks = (n + 255) / 256;
-    AC_REQUIRE(blocks < (1LL << 31), "track too long");
-    hipLaunchKernelGGL(k_mdx_assemble_ola, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
-                       chunk_len, eff_start, eff_end, item_base, n_chunks, vocal_out, inst_out);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Per-chunk mono vocal (what `backend.infer_chunk(...).vocal` is in the reference, backends.py:389-406):
-// the chunked VAD consumes it before the overlap-add (enhanced_vocal_separator.py:412-417).
-// out is the concatenation of all chunks' vocals; out_offset[c] = first element of chunk c.
-__global__ __launch_bounds__(256) void k_mdx_chunk_vocal(const float* __restrict__ wave, const int64_t* __restrict__ chunk_len,
-                                                         const int64_t* __restrict__ out_offset,
-                                                         const int32_t* __restrict__ item_base, float* __restrict__ out) {
-    const int c = blockIdx.y;
-    const int64_t cl = chunk_len[c];
-    float* dst = out + out_offset[c];
-    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < cl; q += (int64_t)gridDim.x * 256) {
-        const int item = item_base[c] + (int)(q / MDX_GEN);
-        const int pos = MDX_TRIM + (int)(q % MDX_GEN);
-        const float w0 = wave[((size_t)item * 2 + 0) * MDX_ITEM + pos];
-        const float w1 = wave[((size_t)item * 2 + 1) * MDX_ITEM + pos];
-        dst[q] = (w0 + w1) * 0.5f;
-    }
-}
-
-extern "C" int ac_mdx_chunk_vocal(ac_ctx* ctx, const float* wave, const int64_t* chunk_len, const int64_t* out_offset,
-                                  const int32_t* item_base, int n_chunks, float* out, void* stream) {
-    AC_REQUIRE(ctx && wave && chunk_len && out_offset && item_base && out, "null pointer");
-    AC_REQUIRE(n_chunks > 0 && n_chunks <= 65535, "n_chunks must be in [1, 65535]");
-    hipLaunchKernelGGL(k_mdx_chunk_vocal, dim3(256, n_chunks), dim3(256), 0, (hipStream_t)stream, wave, chunk_len, out_offset,
-                       item_base, out);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// True stereo stem assembly + overlap-add (include/audiocut_hip_stereo.h): the planar [2][n] mix, the same gather and chunk
-// search as k_mdx_assemble_ola.  Per covering chunk, in chunk order: the mono stems are the channel means in mdx_assemble's
-// order, (w0 + w1) * 0.5 and ((m0 - w0) + (m1 - w1)) * 0.5 (with m0 == m1 exactly k_mdx_assemble_ola's), and the stereo stems
-// accumulate w_c and m_c - w_c per channel; every sum is divided by the same count of covering chunks.
-__global__ __launch_bounds__(256) void k_mdx_assemble_ola_stereo(const float* __restrict__ track, int64_t n, const float* __restrict__ wave,
-                                                                 const int64_t* __restrict__ chunk_start,
-                                                                 const int64_t* __restrict__ chunk_len,
-                                                                 const int64_t* __restrict__ eff_start,
-                                                                 const int64_t* __restrict__ eff_end,
-                                                                 const int32_t* __restrict__ item_base, int n_chunks,
-                                                                 float* __restrict__ vocal_out, float* __restrict__ inst_out,
-                                                                 float* __restrict__ vocal_st_out, float* __restrict__ inst_st_out) {
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (g >= n) return;
-    int lo = 0, hi = n_chunks;              // first chunk with eff_end > g
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (eff_end[mid] > g) hi = mid; else lo = mid + 1; }
-    const int c_lo = lo;
-    const float m0 = track[g], m1 = track[n + g];
+    const float m0 = track[g];
+    const float m1 = CH == 2 ? track[n + g] : m0;
     float v_acc = 0.f, i_acc = 0.f, w_acc = 0.f;
     float v0_acc = 0.f, v1_acc = 0.f, i0_acc = 0.f, i1_acc = 0.f;
     for (int c = c_lo; c < n_chunks && eff_start[c] <= g; ++c) {
@@ -396,18 +276,37 @@ __global__ __launch_bounds__(256) void k_mdx_assemble_ola_stereo(const float* __
         const int pos = MDX_TRIM + (int)(q % MDX_GEN);
         const float w0 = wave[((size_t)item * 2 + 0) * MDX_ITEM + pos];
         const float w1 = wave[((size_t)item * 2 + 1) * MDX_ITEM + pos];
-        const float r0 = m0 - w0, r1 = m1 - w1;
-        v_acc += (w0 + w1) * 0.5f;           // vocal.mean(axis=0) in float32
-        i_acc += (r0 + r1) * 0.5f;           // (mix - vocal).mean(axis=0)
+        const float vocal = (w0 + w1) * 0.5f;                   // vocal.mean(axis=0) in float32
+        const float inst = ((m0 - w0) + (m1 - w1)) * 0.5f;      // (mix - vocal).mean(axis=0)
+        v_acc += vocal;
+        i_acc += inst;
         w_acc += 1.0f;
-        v0_acc += w0; v1_acc += w1;
-        i0_acc += r0; i1_acc += r1;
+        if (CH == 2) {
+            v0_acc += w0; v1_acc += w1;
+            i0_acc += m0 - w0; i1_acc += m1 - w1;
+        }
     }
     if (w_acc == 0.f) w_acc = 1.0f;
     vocal_out[g] = v_acc / w_acc;
     inst_out[g] = i_acc / w_acc;
-    if (vocal_st_out) { vocal_st_out[g] = v0_acc / w_acc; vocal_st_out[n + g] = v1_acc / w_acc; }
-    if (inst_st_out) { inst_st_out[g] = i0_acc / w_acc; inst_st_out[n + g] = i1_acc / w_acc; }
+    if (CH == 2) {
+        if (vocal_st_out) { vocal_st_out[g] = v0_acc / w_acc; vocal_st_out[n + g] = v1_acc / w_acc; }
+        if (inst_st_out) { inst_st_out[g] = i0_acc / w_acc; inst_st_out[n + g] = i1_acc / w_acc; }
+    }
+}
+
+extern "C" int ac_mdx_assemble_ola(ac_ctx* ctx, const float* track, int64_t n, const float* wave, const int64_t* chunk_start,
+                                   const int64_t* chunk_len, const int64_t* eff_start, const int64_t* eff_end,
+                                   const int32_t* item_base, int n_chunks, float* vocal_out, float* inst_out, void* stream) {
+    AC_REQUIRE(ctx && track && wave && chunk_start && chunk_len && eff_start && eff_end && item_base && vocal_out && inst_out,
+               "null pointer");
+    AC_REQUIRE(n > 0 && n_chunks > 0, "sizes must be positive");
+    const int64_t blocks = (n + 255) / 256;
+    AC_REQUIRE(blocks < (1LL << 31), "track too long");
+    hipLaunchKernelGGL(k_mdx_assemble_ola<1>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
+                       chunk_len, eff_start, eff_end, item_base, n_chunks, vocal_out, inst_out, nullptr, nullptr);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
 }
 
 extern "C" int ac_mdx_assemble_ola_stereo(ac_ctx* ctx, const float* track, int64_t n, const float* wave, const int64_t* chunk_start,
@@ -419,32 +318,47 @@ extern "C" int ac_mdx_assemble_ola_stereo(ac_ctx* ctx, const float* track, int64
     AC_REQUIRE(n > 0 && n_chunks > 0, "sizes must be positive");
     const int64_t blocks = (n + 255) / 256;
     AC_REQUIRE(blocks < (1LL << 31), "track too long");
-    hipLaunchKernelGGL(k_mdx_assemble_ola_stereo, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
+    hipLaunchKernelGGL(k_mdx_assemble_ola<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
                        chunk_len, eff_start, eff_end, item_base, n_chunks, vocal_out, inst_out, vocal_st_out, inst_st_out);
     AC_LAUNCH_CHECK();
     return AC_OK;
 }
 
-// Per-chunk mono vocal of a true-stereo track: (w0 + w1) * 0.5, or for an instrumental-type network (mix_minus != 0)
-// ((m0 - w0) + (m1 - w1)) * 0.5 with m_c the planar track's channel c at chunk_start[c] + q - mdx_assemble's order.
-__global__ __launch_bounds__(256) void k_mdx_chunk_vocal_stereo(const float* __restrict__ track, int64_t n, const float* __restrict__ wave,
-                                                                const int64_t* __restrict__ chunk_start,
-                                                                const int64_t* __restrict__ chunk_len,
-                                                                const int64_t* __restrict__ out_offset,
-                                                                const int32_t* __restrict__ item_base, int mix_minus,
-                                                                float* __restrict__ out) {
+// ---------------------------------------------------------------------------------------------
+// Per-chunk mono vocal (what `backend.infer_chunk(...).vocal` is in the reference, backends.py:389-406):
+// the chunked VAD consumes it before the overlap-add (enhanced_vocal_separator.py:412-417).
+// out is the concatenation of all chunks' vocals; out_offset[c] = first element of chunk c.  (w0 + w1) * 0.5, or for a
+// planar [2][n] stereo track and an instrumental-type network (mix_minus != 0) ((m0 - w0) + (m1 - w1)) * 0.5 with m_c the
+// track's channel c at chunk_start[c] + q - mdx_assemble's order.  The mono instantiation never reads track or chunk_start.
+template <int CH>
+__global__ __launch_bounds__(256) void k_mdx_chunk_vocal(const float* __restrict__ track, int64_t n, const float* __restrict__ wave,
+                                                         const int64_t* __restrict__ chunk_start,
+                                                         const int64_t* __restrict__ chunk_len,
+                                                         const int64_t* __restrict__ out_offset,
+                                                         const int32_t* __restrict__ item_base, int mix_minus,
+                                                         float* __restrict__ out) {
     const int c = blockIdx.y;
     const int64_t cl = chunk_len[c];
-    const int64_t cs = chunk_start[c];
+    const int64_t cs = CH == 2 ? chunk_start[c] : 0;
     float* dst = out + out_offset[c];
     for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < cl; q += (int64_t)gridDim.x * 256) {
         const int item = item_base[c] + (int)(q / MDX_GEN);
         const int pos = MDX_TRIM + (int)(q % MDX_GEN);
         const float w0 = wave[((size_t)item * 2 + 0) * MDX_ITEM + pos];
         const float w1 = wave[((size_t)item * 2 + 1) * MDX_ITEM + pos];
-        if (mix_minus) dst[q] = ((track[cs + q] - w0) + (track[n + cs + q] - w1)) * 0.5f;
+        if (CH == 2 && mix_minus) dst[q] = ((track[cs + q] - w0) + (track[n + cs + q] - w1)) * 0.5f;
         else dst[q] = (w0 + w1) * 0.5f;
     }
+}
+
+extern "C" int ac_mdx_chunk_vocal(ac_ctx* ctx, const float* wave, const int64_t* chunk_len, const int64_t* out_offset,
+                                  const int32_t* item_base, int n_chunks, float* out, void* stream) {
+    AC_REQUIRE(ctx && wave && chunk_len && out_offset && item_base && out, "null pointer");
+    AC_REQUIRE(n_chunks > 0 && n_chunks <= 65535, "n_chunks must be in [1, 65535]");
+    hipLaunchKernelGGL(k_mdx_chunk_vocal<1>, dim3(256, n_chunks), dim3(256), 0, (hipStream_t)stream, nullptr, (int64_t)0, wave,
+                       nullptr, chunk_len, out_offset, item_base, 0, out);
+    AC_LAUNCH_CHECK();
+    return AC_OK;
 }
 
 extern "C" int ac_mdx_chunk_vocal_stereo(ac_ctx* ctx, const float* track, int64_t n, const float* wave, const int64_t* chunk_start,
@@ -453,7 +367,7 @@ extern "C" int ac_mdx_chunk_vocal_stereo(ac_ctx* ctx, const float* track, int64_
     AC_REQUIRE(ctx && wave && chunk_start && chunk_len && out_offset && item_base && out, "null pointer");
     AC_REQUIRE(!mix_minus || (track && n > 0), "mix_minus needs the track");
     AC_REQUIRE(n_chunks > 0 && n_chunks <= 65535, "n_chunks must be in [1, 65535]");
-    hipLaunchKernelGGL(k_mdx_chunk_vocal_stereo, dim3(256, n_chunks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
+    hipLaunchKernelGGL(k_mdx_chunk_vocal<2>, dim3(256, n_chunks), dim3(256), 0, (hipStream_t)stream, track, n, wave, chunk_start,
                        chunk_len, out_offset, item_base, mix_minus, out);
     AC_LAUNCH_CHECK();
     return AC_OK;

@@ -278,8 +278,6 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         hip = self.hip
         net = self.net
         d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets = tables
-        stereo = track_dev.dim() == 2
-        stft = hip.mdx_stft_stereo if stereo else hip.mdx_stft
         wave = torch.empty((n_items, 2, ITEM_LEN), dtype=torch.float32, device=hip.device)
         events: List[List[torch.cuda.Event]] = []     # per sub-batch: [before stft, before net, before istft, after istft]
         for a in range(0, n_items, step):
@@ -287,7 +285,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if timings is not None else None
             if ev: ev[0].record()
             amax = torch.zeros((b - a, 256), dtype=torch.float32, device=hip.device)  # max |spec| per item and frame: the first conv's activation scale
-            spec = stft(track_dev, d_cs[a:b].contiguous(), d_cl[a:b].contiguous(), d_wi[a:b].contiguous(), amax=amax)
+            spec = hip.mdx_stft(track_dev, d_cs[a:b].contiguous(), d_cl[a:b].contiguous(), d_wi[a:b].contiguous(), amax=amax)
             if ev: ev[1].record()
             out = net.forward_tf(spec, amax)
             del spec
@@ -297,27 +295,18 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             if ev:
                 ev[3].record()
                 events.append(ev)
-        if stereo:
-            # the mono stems are the channel means of the stereo ones (mdx_assemble's order); the network's stem and mix minus
-            # it swap for an instrumental-type model exactly like the mono ones, and the VAD input becomes mix minus the stem
-            vocal_like, other, vocal_like_st, other_st = hip.mdx_assemble_ola_stereo(track_dev, wave, d_chunk_start, d_chunk_len,
-                                                                                     d_es, d_ee, d_base)
-            vocal_type = self.get_output_type() == "vocal"
-            chunk_vocal = hip.mdx_chunk_vocal_stereo(track_dev, wave, d_chunk_start, d_chunk_len, d_offsets, d_base, int(offsets[-1]),
-                                                     mix_minus=not vocal_type)
-            if vocal_type:
-                return wave, vocal_like, other, chunk_vocal, vocal_like_st, other_st, events
-            return wave, other, vocal_like, chunk_vocal, other_st, vocal_like_st, events
-        vocal_like, other = hip.mdx_assemble_ola(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
-        chunk_vocal = hip.mdx_chunk_vocal(wave, d_chunk_len, d_offsets, d_base, int(offsets[-1]))
-        if self.get_output_type() == "vocal":
-            vocal, inst = vocal_like, other
-        else:
-            # the network output is the instrumental: vocal = mix - wave, and the VAD input follows
-            vocal, inst = other, vocal_like
-            chunk_mix = torch.cat([track_dev[cs:ce] for cs, ce, _, _ in ranges])
-            chunk_vocal = chunk_mix - chunk_vocal
-        return wave, vocal, inst, chunk_vocal, None, None, events
+        # the network's stem and the mix minus it (for a stereo track the mono stems are the channel means of the stereo ones, in
+        # mdx_assemble's order); an instrumental-type network swaps them, and the VAD input becomes the mix minus its stem
+        stem, rest, stem_st, rest_st = hip.mdx_assemble_ola(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
+        vocal_type = self.get_output_type() == "vocal"
+        mono = track_dev.dim() == 1
+        chunk_vocal = hip.mdx_chunk_vocal(track_dev, wave, d_chunk_start, d_chunk_len, d_offsets, d_base, int(offsets[-1]),
+                                          mix_minus=not (vocal_type or mono))
+        if vocal_type:
+            return wave, stem, rest, chunk_vocal, stem_st, rest_st, events
+        if mono:        # m - (w0 + w1) * 0.5, not the stereo kernel's ((m - w0) + (m - w1)) * 0.5 ("L == R")
+            chunk_vocal = torch.cat([track_dev[cs:ce] for cs, ce, _, _ in ranges]) - chunk_vocal
+        return wave, rest, stem, chunk_vocal, rest_st, stem_st, events
 
     # -- reference-shaped per-chunk call ----------------------------------------------------------
     def infer_chunk(self, mix_chunk: np.ndarray, **kwargs) -> SeparationOutputs:

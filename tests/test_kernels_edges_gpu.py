@@ -262,8 +262,12 @@ def test_mdx_chunk_vocal_edges(hip_ctx):
         offsets = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
         gen = torch.Generator(device=hip_ctx.device).manual_seed(11)
         wave = torch.randn((int(sum(n_it)), 2, ITEM), generator=gen, device=hip_ctx.device)
-        got = hip_ctx.mdx_chunk_vocal(wave, hip_ctx.to_device(np.asarray(lens, np.int64)), hip_ctx.to_device(offsets[:-1].copy()),
-                                      hip_ctx.to_device(base), int(offsets[-1])).cpu().numpy()
+        track = torch.zeros(int(offsets[-1]), dtype=torch.float32, device=hip_ctx.device)    # chunks back to back; never read
+        args = (track, wave, hip_ctx.to_device(offsets[:-1].copy()), hip_ctx.to_device(np.asarray(lens, np.int64)),
+                hip_ctx.to_device(offsets[:-1].copy()), hip_ctx.to_device(base), int(offsets[-1]))
+        got = hip_ctx.mdx_chunk_vocal(*args).cpu().numpy()
+        with pytest.raises(_native.NativeError):      # the mono entry point has no mix-minus form
+            hip_ctx.mdx_chunk_vocal(*args, mix_minus=True)
         w = wave.cpu().numpy()
         for c, cl in enumerate(lens):
             q = np.arange(cl)
@@ -276,7 +280,7 @@ def test_mdx_chunk_vocal_edges(hip_ctx):
                 aligned = cl + (-cl) % 4096
                 vocal, _ = OC.mdx_assemble(w[base[c]: base[c] + n_it[c]], np.zeros((2, aligned), np.float32), cl)
                 assert np.array_equal(seg, vocal), c
-        del wave, w
+        del wave, w, track
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -222,13 +222,14 @@ def test_mdx_stft_istft_assemble(hip_ctx, song):
         outs.append(OC.mdx_assemble(ref_wave[k0:k0 + nb], stereo, orig))
         k0 += nb
     ref_v, ref_i = OC.overlap_add(len(x), ranges, outs)
-    v, i = hip_ctx.mdx_assemble_ola(
+    v, i, v_st, i_st = hip_ctx.mdx_assemble_ola(
         xd, hip_ctx.to_device(ref_wave), hip_ctx.to_device(np.array([r[0] for r in ranges], np.int64)),
         hip_ctx.to_device(np.array([r[1] - r[0] for r in ranges], np.int64)),
         hip_ctx.to_device(np.array([r[2] for r in ranges], np.int64)),
         hip_ctx.to_device(np.array([r[3] for r in ranges], np.int64)), hip_ctx.to_device(np.array(base, np.int32)))
     assert np.array_equal(v.cpu().numpy(), ref_v)
     assert np.array_equal(i.cpu().numpy(), ref_i)
+    assert v_st is None and i_st is None                         # a mono track has no stereo stems
 
 
 def test_yin_f0_autocorrelation_kernel(hip_ctx):

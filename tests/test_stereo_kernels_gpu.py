@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from audio_cut_amd._native import NativeError
 from audio_cut_amd.testing import signals
 from oracle import chunking as OC, separator as OS
 
@@ -49,7 +50,7 @@ def test_mdx_stft_stereo_against_oracle(hip_ctx, stereo):
     ref = torch.cat([OS.mdx_stft(items[(cs, ce)][0]) for cs, ce, _, _ in ranges])        # [items, 4, F, T]
     xd = hip_ctx.to_device(x)
     amax = torch.zeros((d_cs.numel(), 256), dtype=torch.float32, device=hip_ctx.device)
-    spec = hip_ctx.mdx_stft_stereo(xd, d_cs, d_cl, d_wi, amax=amax)
+    spec = hip_ctx.mdx_stft(xd, d_cs, d_cl, d_wi, amax=amax)
     got = spec.permute(0, 1, 3, 2).cpu().numpy()
     assert _rel(got, ref.numpy()) < 2e-6
     assert not np.array_equal(got[:, 0], got[:, 2])                                       # L and R really differ
@@ -59,8 +60,12 @@ def test_mdx_stft_stereo_against_oracle(hip_ctx, stereo):
     xm = x[0]
     am_m = torch.zeros_like(amax); am_s = torch.zeros_like(amax)
     mono = hip_ctx.mdx_stft(hip_ctx.to_device(xm), d_cs, d_cl, d_wi, amax=am_m)
-    dup = hip_ctx.mdx_stft_stereo(hip_ctx.to_device(np.stack([xm, xm])), d_cs, d_cl, d_wi, amax=am_s)
+    dup = hip_ctx.mdx_stft(hip_ctx.to_device(np.stack([xm, xm])), d_cs, d_cl, d_wi, amax=am_s)
     assert torch.equal(mono, dup) and torch.equal(am_m, am_s)
+    # a track is [n] or a contiguous planar [2, n]: anything else is refused
+    for bad in (xd.t().contiguous(), xd[:, ::2], torch.stack([xd[0]] * 3)):
+        with pytest.raises(NativeError):
+            hip_ctx.mdx_stft(bad, d_cs, d_cl, d_wi)
 
 
 def _restated_stereo_ola(x, wave, ranges, base, nbs):
@@ -94,15 +99,15 @@ def test_mdx_assemble_ola_stereo_exact(hip_ctx, stereo):
         k0 += batch.shape[0]
     ref_v, ref_i = OC.overlap_add(x.shape[1], ranges, outs)
     xd = hip_ctx.to_device(x)
-    v, i, vs, is_ = hip_ctx.mdx_assemble_ola_stereo(xd, hip_ctx.to_device(wave), d_start, d_len, d_es, d_ee, d_base)
+    v, i, vs, is_ = hip_ctx.mdx_assemble_ola(xd, hip_ctx.to_device(wave), d_start, d_len, d_es, d_ee, d_base)
     assert np.array_equal(v.cpu().numpy(), ref_v)
     assert np.array_equal(i.cpu().numpy(), ref_i)
     rv, ri = _restated_stereo_ola(x, wave, ranges, base, nbs)
     assert np.array_equal(vs.cpu().numpy(), rv)
     assert np.array_equal(is_.cpu().numpy(), ri)
     # the stems can be skipped: the mono outputs do not change
-    v2, i2, none_v, none_i = hip_ctx.mdx_assemble_ola_stereo(xd, hip_ctx.to_device(wave), d_start, d_len, d_es, d_ee, d_base,
-                                                              stereo_stems=False)
+    v2, i2, none_v, none_i = hip_ctx.mdx_assemble_ola(xd, hip_ctx.to_device(wave), d_start, d_len, d_es, d_ee, d_base,
+                                                       stereo_stems=False)
     assert none_v is None and none_i is None and torch.equal(v, v2) and torch.equal(i, i2)
 
 
@@ -116,8 +121,8 @@ def test_mdx_chunk_vocal_stereo_exact(hip_ctx, stereo):
     offsets = np.concatenate(([0], np.cumsum(lens))).astype(np.int64)
     xd, wd = hip_ctx.to_device(x), hip_ctx.to_device(wave)
     for mix_minus in (False, True):
-        got = hip_ctx.mdx_chunk_vocal_stereo(xd, wd, d_start, d_len, hip_ctx.to_device(offsets[:-1]), d_base, int(offsets[-1]),
-                                             mix_minus=mix_minus).cpu().numpy()
+        got = hip_ctx.mdx_chunk_vocal(xd, wd, d_start, d_len, hip_ctx.to_device(offsets[:-1]), d_base, int(offsets[-1]),
+                                      mix_minus=mix_minus).cpu().numpy()
         k0 = 0
         for c, (cs, ce, _, _) in enumerate(ranges):
             batch, st, orig = items[(cs, ce)]

@@ -6,7 +6,7 @@ planar (2, N) track, alternated in one process after both are warm.
 Track: the seeded `signals.c2_song(240, seed=2, stereo=True)`; full-size TFC-TDF with seeded synthetic weights, 64 items per
 forward (the library default).  Prints one JSON line: ms per track for each path (median, min, max over the steps) and the
 stereo - mono difference of the medians.  Under `rocprofv3 --kernel-trace --stats -- python tools/stereo_step.py` the kernel
-statistics give the per-kernel times (k_mdx_stft vs k_mdx_stft_stereo, ...)."""
+statistics give the per-kernel times (k_mdx_stft<1> vs k_mdx_stft<2>, ...)."""
 from __future__ import annotations
 
 import argparse
