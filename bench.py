@@ -14,14 +14,20 @@ Every step is a DIFFERENT track.  N = 1: seed 2 (the C2 track) first, then the C
 process per GPU; the N * K tracks of the job are the C3 seeds 100 .. 100 + N * K - 1 (N = 8, K = 4 is
 BASELINE configs[2] itself: 32 x 4-min tracks), dealt to the ranks by `audio_cut_amd.batch.assign_tracks` (weak
 scaling; tracks are independent, no data-path collective), batch completion = RCCL barrier + all_gather_object of
-per-track summaries.  Every track's boundary SHA-1 is compared with the committed single-GPU result of the same seed
-(tests/golden/c3_n1_sha1.json, written by `bench.py --config c3 --write-golden PATH`): "per-track boundaries identical to
-the single-GPU run" is checked inside the bench (`parity_vs_single_gpu`).  `--gpus N` without a launcher starts the
-N ranks itself (child processes, before anything touches the GPU).
+per-track summaries.  `--gpus N` without a launcher starts the N ranks itself (child processes, before anything touches
+the GPU).
   --config c3   32 tracks (seeds 100-131) over the ranks present, K = 32 / N per rank
   --config c5   BASELINE configs[4]: one 30-min track per step (240 chunks, 480 U-Net items)
   --dump-outputs DIR   what the last timed step returned, as DIR/<name>.npy (dump_outputs), for comparing two builds
+  --full        also what the headline figure does not need (below)
 Rank 0 prints ONE JSON line; `ms_per_step` is the timed region's wall time over the K timed steps.
+
+A plain run sets up (the tracks are generated on a thread pool), warms up, times the K steps, writes --dump-outputs and
+prints the line.  `--full` adds, after the timed region: the parity checks - every track's boundary SHA-1 against the
+committed single-GPU result of the same seed (tests/golden/c3_n1_sha1.json, written by `bench.py --config c3 --write-golden
+PATH`; `parity_vs_single_gpu`) and the seed-2 track against the CPU oracle's fixture, non-zero exit on a mismatch - and,
+on one GPU, the single-stream latency, the framewise kernel rooflines with the fused-pass accounting, and the CPU baseline
+(`--cpu-baseline-seconds`).
 """
 from __future__ import annotations
 
@@ -30,6 +36,7 @@ import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -43,6 +50,13 @@ METRIC = "audio-seconds processed/sec (separate+detect) per GPU; cut-point index
 F32_MATRIX_PEAK_TFLOPS = 157.3        # MI355X_MICROARCH.md: peak FP32 (matrix), v_mfma_f32_32x32x2_f32
 
 
+def _host_cores() -> int:
+    try:
+        return len(os.sched_getaffinity(0))
+    except AttributeError:
+        return os.cpu_count() or 1
+
+
 def cpu_baseline(sample_s: float, weights, spec, single_thread_sample_s: float = 10.0) -> dict:
     """The oracle (CPU restatement of the reference path: torch-CPU STFT/U-Net/iSTFT + numpy detection and
     guard) timed on this host's cores on a bounded sample of the same workload: once on the GPU's share of the host cores
@@ -52,11 +66,7 @@ def cpu_baseline(sample_s: float, weights, spec, single_thread_sample_s: float =
     from oracle import e2e as OE, refine as OR
     OR.LEGACY_PROMOTION = True
     # the GPU box shares its host: one GPU's CPU share is 16 cores, whatever os.cpu_count() says
-    try:
-        avail = len(os.sched_getaffinity(0))
-    except AttributeError:
-        avail = os.cpu_count() or 1
-    threads = int(os.environ.get("AC_CPU_BASELINE_THREADS", min(16, avail)))
+    threads = int(os.environ.get("AC_CPU_BASELINE_THREADS", min(16, _host_cores())))
     saved = torch.get_num_threads()
 
     def leg(seconds: float, n_threads: int) -> dict:
@@ -350,6 +360,38 @@ C3_SEED0 = 100                         # C3 = 32 x C2 with seeds 1
 C3_GOLDEN = ROOT / "tests" / "golden" / "c3_n1_sha1.json"
 
 
+def check_parity(config: str, track_s: float, all_summaries: list, step_results: list, summaries: list, c4_fixture: Path):
+    """--full: the timed tracks' results against the committed references; returns the `parity_vs_single_gpu` block and whether
+    everything that was checked agreed."""
+    # "per-track boundaries identical to the single-GPU run" (SURVEY.md 8d C3): every track against the committed N = 1 result
+    golden = {}
+    if C3_GOLDEN.exists() and config in ("c2", "c3") and track_s == 240.0:
+        golden = json.loads(C3_GOLDEN.read_text()).get("tracks", {})
+    checked = [(d, golden[str(d["seed"])]) for d in all_summaries if str(d["seed"]) in golden]
+    bad = [d["seed"] for d, g in checked if d["boundaries_sha1"] != g["boundaries_sha1"] or d["cuts_sha1"] != g["cuts_sha1"]]
+    parity = {"reference": "tests/golden/c3_n1_sha1.json (bench.py --config c3 --write-golden on one GPU)" if golden else None,
+              "tracks_checked": len(checked), "tracks_identical": len(checked) - len(bad), "mismatched_seeds": bad,
+              "unchecked_seeds": [d["seed"] for d in all_summaries if str(d["seed"]) not in golden]}
+    # the seed-2 track is BASELINE configs[1] / [3] itself: its guard boundaries and manifest cuts against the CPU oracle's
+    # committed result (tests/golden/c2_full_oracle.npz, c4_full_oracle.npz: data, written by tests/golden/make_*.py)
+    oracle_fx = {"c2": ROOT / "tests" / "golden" / "c2_full_oracle.npz", "c4": c4_fixture}.get(config)
+    vs_oracle = None
+    if oracle_fx is not None and oracle_fx.exists() and track_s == 240.0:
+        for st_res, d in zip(step_results, summaries):
+            if d["seed"] == 2:
+                fx = np.load(oracle_fx)
+                vs_oracle = {"fixture": str(oracle_fx.relative_to(ROOT)), "seed": 2,
+                             "boundaries_exact": [int(v) for v in st_res["sample_boundaries"]] == fx["sample_boundaries"].tolist(),
+                             "manifest_cuts_exact": [int(v) for v in st_res.get("cuts_samples", [])] == fx["cuts"].tolist(),
+                             "n_boundaries": int(len(fx["sample_boundaries"]))}
+                if config == "c4":
+                    vs_oracle["vpbd_selected_exact"] = list(st_res.get("vpbd_selected_times", [])) == fx["vpbd_selected"][:, 0].tolist()
+                    vs_oracle["vad_segments"] = len(st_res.get("vad_segments") or [])
+    parity["vs_cpu_oracle_fixture"] = vs_oracle
+    parity_ok = (not bad) and (vs_oracle is None or all(v for k, v in vs_oracle.items() if k.endswith("_exact")))
+    return parity, parity_ok
+
+
 def _launch_ranks(n: int, argv: list) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as child processes of a torch.distributed.run child
     (never an exec of this process; nothing here has touched the GPU yet) and return its exit code."""
@@ -376,9 +418,13 @@ def main() -> None:
                     help="U-Net windows per forward; default 64 (a 4-min track in one forward: -1.2 %% per track), 32 for --config c4: with two "
                          "tracks in flight the long VPBD / Silero tail of one track runs beside the other's U-Net, and behind 2x longer launches "
                          "its small kernels wait longer (profiles/r04ak)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also check parity against the committed single-GPU table and the CPU oracle's fixture "
+                         "(exit 3 on a mismatch) and, on one GPU, measure the single-stream latency, the framewise kernel rooflines and "
+                         "the CPU baseline; a plain run does none of these")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=240.0,
-                    help="length of the C2 track's prefix the CPU oracle is timed on (default: the whole 240 s track, about 170 s of CPU "
-                         "on 16 threads); 0 disables the CPU baseline leg")
+                    help="with --full: length of the C2 track's prefix the CPU oracle is timed on (default: the whole 240 s track, about "
+                         "170 s of CPU on 16 threads); 0 disables the CPU baseline leg")
     ap.add_argument("--pipeline-depth", type=int, default=2,
                     help="tracks in flight per GPU (audio_cut_amd.batch.TrackPipeline): 1 = strictly one after the other")
     ap.add_argument("--no-separation-gate", action="store_true",
@@ -441,11 +487,6 @@ def main() -> None:
     from audio_cut_amd.testing import signals
 
     sr = 44100
-    spec = TfcTdfSpec()
-    weights = synth_weights(spec, seed=0)
-    hip = _native.Context(device)
-    backend = MDX23HipBackend(weights=weights, ctx=hip, max_items_per_forward=args.items_per_forward)
-    backend.load_model()
 
     # ---- the job: which tracks, which of them are mine ------------------------------------------------------------------
     track_s = float(args.track_seconds if args.track_seconds is not None else (1800.0 if args.config == "c5" else 240.0))
@@ -464,6 +505,18 @@ def main() -> None:
     assert len(mine) == steps
     make = (lambda sd: signals.c5_long_form(track_s, seed=sd)) if args.config == "c5" else (lambda sd: signals.c2_song(track_s, seed=sd))
     depth = max(1, min(int(args.pipeline_depth), steps))
+    n_warm = max(args.warmup, depth) if args.warmup > 0 else 0
+    # the tracks are generated on a thread pool (the generators are numpy-bound and release the GIL; every track has its own seeded
+    # rng, so it is the same array whichever thread makes it) while the weights are built and loaded; 16 cores per GPU at most
+    gen = ThreadPoolExecutor(max_workers=max(1, min(16, _host_cores() // world)))
+    timed_gen = [gen.submit(make, seeds[i]) for i in mine]
+    warm_gen = [gen.submit(make, 50 + k) for k in range(min(n_warm, 2))]      # warm-up tracks: seeds 50, 51
+
+    spec = TfcTdfSpec()
+    weights = synth_weights(spec, seed=0)
+    hip = _native.Context(device)
+    backend = MDX23HipBackend(weights=weights, ctx=hip, max_items_per_forward=args.items_per_forward)
+    backend.load_model()
     mode = "vpbd_acoustic" if args.config == "c4" else "v2.2_mdd"
     c4_fixture = ROOT / "tests" / "golden" / "c4_full_oracle.npz"
     vad_fn = None
@@ -485,11 +538,11 @@ def main() -> None:
 
     # every timed track is generated and made resident in HBM before the clock starts (BASELINE contract); warm-up tracks are
     # tracks of their own (seeds 50, 51, ...) so nothing of a timed track has been seen before
-    tracks = [make(seeds[i]) for i in mine]
+    tracks = [f.result() for f in timed_gen]
     tracks_dev = [hip.to_device(m) for m in tracks]
-    n_warm = max(args.warmup, depth) if args.warmup > 0 else 0
+    warm = [f.result() for f in warm_gen]
+    gen.shutdown()
     if n_warm:
-        warm = [make(50 + (k % 2)) for k in range(min(n_warm, 2))]
         warm_dev = [hip.to_device(m) for m in warm]
         pipeline.run([job_for(warm[k % len(warm)], warm_dev[k % len(warm)]) for k in range(n_warm)])   # every worker (stream, allocator pools) warms up
         del warm, warm_dev
@@ -539,32 +592,7 @@ def main() -> None:
         total_audio = track_s * steps * world
         flops = spec.flops_per_item() * items
         achieved = flops / (unet_ms / 1e3) / 1e12 if unet_ms > 0 else 0.0
-        # "per-track boundaries identical to the single-GPU run" (SURVEY.md 8d C3): every track against the committed N = 1 result
-        golden = {}
-        if C3_GOLDEN.exists() and args.config in ("c2", "c3") and track_s == 240.0:
-            golden = json.loads(C3_GOLDEN.read_text()).get("tracks", {})
-        checked = [(d, golden[str(d["seed"])]) for d in all_summaries if str(d["seed"]) in golden]
-        bad = [d["seed"] for d, g in checked if d["boundaries_sha1"] != g["boundaries_sha1"] or d["cuts_sha1"] != g["cuts_sha1"]]
-        parity = {"reference": "tests/golden/c3_n1_sha1.json (bench.py --config c3 --write-golden on one GPU)" if golden else None,
-                  "tracks_checked": len(checked), "tracks_identical": len(checked) - len(bad), "mismatched_seeds": bad,
-                  "unchecked_seeds": [d["seed"] for d in all_summaries if str(d["seed"]) not in golden]}
-        # the seed-2 track is BASELINE configs[1] / [3] itself: its guard boundaries and manifest cuts against the CPU oracle's
-        # committed result (tests/golden/c2_full_oracle.npz, c4_full_oracle.npz: data, written by tests/golden/make_*.py)
-        oracle_fx = {"c2": ROOT / "tests" / "golden" / "c2_full_oracle.npz", "c4": c4_fixture}.get(args.config)
-        vs_oracle = None
-        if oracle_fx is not None and oracle_fx.exists() and track_s == 240.0:
-            for st_res, d in zip(step_results, summaries):
-                if d["seed"] == 2:
-                    fx = np.load(oracle_fx)
-                    vs_oracle = {"fixture": str(oracle_fx.relative_to(ROOT)), "seed": 2,
-                                 "boundaries_exact": [int(v) for v in st_res["sample_boundaries"]] == fx["sample_boundaries"].tolist(),
-                                 "manifest_cuts_exact": [int(v) for v in st_res.get("cuts_samples", [])] == fx["cuts"].tolist(),
-                                 "n_boundaries": int(len(fx["sample_boundaries"]))}
-                    if args.config == "c4":
-                        vs_oracle["vpbd_selected_exact"] = list(st_res.get("vpbd_selected_times", [])) == fx["vpbd_selected"][:, 0].tolist()
-                        vs_oracle["vad_segments"] = len(st_res.get("vad_segments") or [])
-        parity["vs_cpu_oracle_fixture"] = vs_oracle
-        parity_ok = (not bad) and (vs_oracle is None or all(v for k, v in vs_oracle.items() if k.endswith("_exact")))
+        parity, parity_ok = check_parity(args.config, track_s, all_summaries, step_results, summaries, c4_fixture) if args.full else (None, True)
         if args.write_golden and args.config == "c3" and world == 1:
             Path(args.write_golden).write_text(json.dumps({"what": "per-track SHA-1 of the guard boundaries and of the manifest cuts of the 32 C3 tracks "
                                                      "(c2_song 240 s, seeds 100-131, synth weights seed 0), one MI355X, bench.py --config c3",
@@ -586,7 +614,7 @@ def main() -> None:
             "metric": METRIC, "value": round(total_audio / elapsed, 3), "unit": "audio-s/s", "n_gpus": world,
             "value_is": "WHOLE-JOB aggregate over n_gpus (all ranks' audio seconds / max-over-ranks wall time), as the bench contract "
                         "prescribes; divide by n_gpus for the per-GPU figure the metric's name refers to",
-            "value_per_gpu": round(total_audio / elapsed / world, 3), "parity_ok": bool(parity_ok),
+            "value_per_gpu": round(total_audio / elapsed / world, 3),
             "batch_completion": ({"backend": dist.get_backend(), "collectives": "barrier, all_reduce(MAX), all_gather_object",
                                   "summaries_gathered": len(all_summaries)} if use_dist else None),
             "steps": steps, "warmup": args.warmup, "ms_per_step": round(elapsed / steps * 1e3, 2),
@@ -616,11 +644,14 @@ def main() -> None:
                                    "mdx_istft": round(istft_ms / steps, 2)},
             "n_boundaries": all_summaries[0]["n_boundaries"], "boundaries_sha1": all_summaries[0]["boundaries_sha1"],
             "n_manifest_cuts": len(step_results[0].get("cuts_samples", [])), "segment_layout_applied": bool(step_results[0].get("segment_layout_applied", False)),
-            "tracks_completed": len(all_summaries), "parity_vs_single_gpu": parity,
+            "tracks_completed": len(all_summaries),
             "track_hashes": {str(d["seed"]): {"boundaries_sha1": d["boundaries_sha1"], "cuts_sha1": d["cuts_sha1"], "n_boundaries": d["n_boundaries"]}
                              for d in all_summaries},
         }
-        if world == 1:
+        if args.full:
+            out["parity_ok"] = bool(parity_ok)
+            out["parity_vs_single_gpu"] = parity
+        if world == 1 and args.full:
             # single-stream latency next to the pipelined throughput: one more track, strictly alone on the GPU (outside the timed region)
             lat_ms = []
             for _ in range(3):           # the median of three: a single probe caught allocator / clock hiccups of 2-3x now and then
@@ -634,7 +665,7 @@ def main() -> None:
                 str([round(v, 1) for v in lat_ms]) + "; same result: " + str(lat["sample_boundaries"] == step_results[0]["sample_boundaries"])
             out["framewise_rooflines"] = framewise_rooflines(hip, tracks_dev[0])
             out.update(framewise_accounting(int(tracks_dev[0].numel())))
-        if world == 1 and args.cpu_baseline_seconds > 0:
+        if world == 1 and args.full and args.cpu_baseline_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, weights, spec)
         out["socket_under_load"] = socket_state
         if dumped is not None:
@@ -642,8 +673,8 @@ def main() -> None:
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()
-    # a throughput figure on top of boundaries that differ from the committed single-GPU / CPU-oracle results is not a result:
-    # fail the run.  That includes the one-GPU rehearsal of the N > 1 control flow (AC_BENCH_REHEARSAL=1, ranks sharing one device):
+    # --full: a throughput figure on top of boundaries that differ from the committed single-GPU / CPU-oracle results is not a
+    # result: fail the run.  That includes the one-GPU rehearsal of the N > 1 control flow (AC_BENCH_REHEARSAL=1, ranks sharing one device):
     # the corruption that mode showed in round 2 was a kernel-level defect, found and removed in round 3.
     if rank == 0 and not parity_ok:
         raise SystemExit(3)

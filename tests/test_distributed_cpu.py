@@ -38,7 +38,7 @@ def test_two_rank_track_sharding(tmp_path):
 
 
 def test_c3_single_gpu_table_agrees_with_the_cpu_oracle(golden_dir=None):
-    """tests/golden/c3_n1_sha1.json (the per-track result of the 32 C3 tracks on one MI355X, what `bench.py --gpus N` checks
+    """tests/golden/c3_n1_sha1.json (the per-track result of the 32 C3 tracks on one MI355X, what `bench.py --gpus N --full` checks
     every rank's tracks against) hashes the SAME integers the CPU oracle produced for the two tracks it was run on
     (c3_seed100_oracle.npz, c3_seed131_oracle.npz: 4 min of oracle time each): guard boundaries and manifest cuts."""
     import hashlib

@@ -543,7 +543,7 @@ def test_c5_loader_leg_48k_stereo_at_full_length(hip_ctx):
 def test_c3_batch_of_32_tracks_on_one_gpu(hip_ctx, golden_dir):
     """BASELINE configs[2] on one GPU: the 32 C3 tracks (c2_song, seeds 100-131) through `batch.TrackPipeline` exactly as
     `bench.py --config c3` runs them.  Every track's guard boundaries and manifest cuts hash to the committed single-GPU
-    result (tests/golden/c3_n1_sha1.json - the table `bench.py --gpus N` checks every rank's tracks against), the LPT deal
+    result (tests/golden/c3_n1_sha1.json - the table `bench.py --gpus N --full` checks every rank's tracks against), the LPT deal
     over 8 ranks is the C3 sharding (4 tracks each), and the first and last track are also checked against the CPU oracle
     (tests/golden/c3_seed100_oracle.npz, c3_seed131_oracle.npz)."""
     import json

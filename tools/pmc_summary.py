@@ -3,8 +3,8 @@
 
 Collection (MI355X_MICROARCH.md §HBM / §rocprofv3 PMC slots): the two counters need separate passes
 (FETCH_SIZE takes 3 TCC slots, WRITE_SIZE 2), each run with --pmc only:
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python bench.py --steps 1 --warmup 1 --cpu-baseline-seconds 0
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python bench.py --steps 1 --warmup 1 --cpu-baseline-seconds 0
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d pmc_fetch -- python bench.py --full --steps 1 --warmup 1 --cpu-baseline-seconds 0
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d pmc_write -- python bench.py --full --steps 1 --warmup 1 --cpu-baseline-seconds 0
 Correction for gfx950: counter unit is KiB; FETCH_SIZE reports exactly half the bytes of a wide coalesced
 streaming read, so read bytes = 2 * FETCH_SIZE * 1024; WRITE_SIZE is exact for 16-byte-per-lane stores.
 Usage: tools/pmc_summary.py <fetch counter_collection.csv> <write counter_collection.csv> <out.json>

@@ -11,7 +11,7 @@
 #   tdf_levels[:lib]    tools/tdf_tile_bench.py 32
 #   unet_tests[:lib]    tests/test_unet_gpu.py
 #   gpu_tests           the whole -m gpu suite
-#   bench[:args]        bench.py --steps 10 --warmup 2 --cpu-baseline-seconds 0 (args: comma-separated extra flags) -> gpurun_out/<tag>_bench.json
+#   bench[:args]        bench.py --full --steps 10 --warmup 2 --cpu-baseline-seconds 0 (args: comma-separated extra flags) -> <tag>_bench.json
 #   bench_default       python bench.py (the driver's command) -> gpurun_out/<tag>_bench_default.json
 #   trace               rocprofv3 --kernel-trace --stats of the bench -> <tag>_bench_kernel_stats.csv, <tag>_bench_kernel_gaps.txt
 #   tail_trace          kernel + copy trace of bench.py --pipeline-depth 1 -> <tag>_track_tail.txt (what runs after a track's U-Net)
@@ -73,7 +73,7 @@ PY
     unet_tests) [ -n "$ARG" ] && export AUDIOCUT_HIP_LIBNAME=$(libenv $ARG); timeout -k 10 700 python -m pytest tests/test_unet_gpu.py -m gpu -x -q >> $L 2>&1 || { tail -30 $L; exit 1; } ;;
     gpu_tests)  timeout -k 10 1100 python -m pytest tests -m gpu -q --durations=15 >> $L 2>&1 || { tail -40 $L; exit 1; }; tail -3 $L ;;
     bench)
-      timeout -k 10 600 python bench.py --steps 10 --warmup 2 --cpu-baseline-seconds 0 ${ARG//,/ } > $O/${TAG}_bench.json 2>> $L || { tail -5 $L; exit 1; }
+      timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 --cpu-baseline-seconds 0 ${ARG//,/ } > $O/${TAG}_bench.json 2>> $L || { tail -5 $L; exit 1; }
       python3 - $O/${TAG}_bench.json >> $L <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -83,21 +83,21 @@ PY
     bench_default) ( time timeout -k 10 900 python bench.py > $O/${TAG}_bench_default.json ) 2>> $L || { tail -5 $L; exit 1; } ;;
     trace)
       rm -rf $O/tr
-      ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/tr -- python3 $R/bench.py --steps 10 --warmup 2 --cpu-baseline-seconds 0 > $O/${TAG}_bench_under_rocprof.json 2>> $L ) || exit 1
+      ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $O/tr -- python3 $R/bench.py --full --steps 10 --warmup 2 --cpu-baseline-seconds 0 > $O/${TAG}_bench_under_rocprof.json 2>> $L ) || exit 1
       DB=$(find $O/tr -name "*.db" | head -1)
       python3 tools/kernel_stats_from_db.py $DB $O/${TAG}_bench_kernel_stats.csv >> $L 2>&1
       python3 tools/kernel_gaps.py $DB 20 12 14 > $O/${TAG}_bench_kernel_gaps.txt 2>&1
       rm -rf $O/tr ;;
     tail_trace)
       rm -rf $O/tr
-      ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace -d $O/tr -- python3 $R/bench.py --steps 3 --warmup 1 --pipeline-depth 1 --cpu-baseline-seconds 0 > $O/${TAG}_bench_depth1.json 2>> $L ) || exit 1
+      ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace -d $O/tr -- python3 $R/bench.py --full --steps 3 --warmup 1 --pipeline-depth 1 --cpu-baseline-seconds 0 > $O/${TAG}_bench_depth1.json 2>> $L ) || exit 1
       python3 tools/track_tail_timeline.py $(find $O/tr -name "*.db" | head -1) 2 > $O/${TAG}_track_tail.txt 2>&1
       tail -25 $O/${TAG}_track_tail.txt >> $L
       rm -rf $O/tr ;;
     pmc)
       rm -rf $O/pf $O/pw
-      ( cd /tmp && timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -- python3 $R/bench.py --steps 1 --warmup 1 --cpu-baseline-seconds 0 > /dev/null 2>> $L ) || exit 1
-      ( cd /tmp && timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -- python3 $R/bench.py --steps 1 --warmup 1 --cpu-baseline-seconds 0 > /dev/null 2>> $L ) || exit 1
+      ( cd /tmp && timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pf -- python3 $R/bench.py --full --steps 1 --warmup 1 --cpu-baseline-seconds 0 > /dev/null 2>> $L ) || exit 1
+      ( cd /tmp && timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pw -- python3 $R/bench.py --full --steps 1 --warmup 1 --cpu-baseline-seconds 0 > /dev/null 2>> $L ) || exit 1
       python3 tools/pmc_summary.py $(find $O/pf -name "*counter_collection.csv" | head -1) $(find $O/pw -name "*counter_collection.csv" | head -1) $O/${TAG}_pmc_summary.json >> $L 2>&1
       rm -rf $O/pf $O/pw ;;
     sq_probe)           # where the waves of the big U-Net kernels spend their cycles: three --pmc passes of 8 SQ counters each
@@ -115,7 +115,7 @@ PY
     configs)
       for CFG in c3 c4 c5; do
         ST=8; [ $CFG = c3 ] && ST=32; [ $CFG = c5 ] && ST=3
-        timeout -k 10 500 python bench.py --config $CFG --steps $ST --warmup 2 --cpu-baseline-seconds 0 > $O/${TAG}_bench_$CFG.json 2>> $L || { tail -5 $L; exit 1; }
+        timeout -k 10 500 python bench.py --full --config $CFG --steps $ST --warmup 2 --cpu-baseline-seconds 0 > $O/${TAG}_bench_$CFG.json 2>> $L || { tail -5 $L; exit 1; }
       done ;;
     pytest) timeout -k 10 1100 python -m pytest ${ARG//,/ } -m gpu -x -q >> $L 2>&1 || { tail -40 $L; exit 1; }; tail -2 $L ;;
     py) S=${ARG%%:*}; A=""; [ "$ARG" != "$S" ] && A=${ARG#*:}; timeout -k 10 900 python tools/$S.py ${A//,/ } >> $L 2>&1 || { tail -20 $L; exit 1; } ;;
