@@ -48,8 +48,9 @@ def queue_mix_globals(hip, mix_dev, sr: int) -> Optional[float]:
     hop = max(1, int(0.01 * sr))
     rms = hip.prefetch("frame_rms", mix_dev, 2048, hop, True).cpu().numpy()              # SeamlessSplitter._rms2048_db (asked again by _finalize_and_filter_cuts_v2)
     floor_db = guard_floor_db(20.0 * np.log10(rms + 1e-12))
-    db = hip.prefetch("moving_meansq_db", mix_dev, guard_window_samples(sr))
-    hip.prefetch("next_leq_scan", db, float(floor_db))
+    if int(mix_dev.numel()) >= guard_window_samples(sr):                                # a shorter wave's lookup is built on the host
+        db = hip.prefetch("moving_meansq_db", mix_dev, guard_window_samples(sr))
+        hip.prefetch("next_leq_scan", db, float(floor_db))
     return floor_db
 
 
@@ -75,6 +76,6 @@ def queue_vocal_globals(hip, vocal_dev, inst_dev, sr: int, floor_db: Optional[fl
         hip.prefetch_frame_rms_multi(vocal_dev, rms_cfgs)
     if relative:
         hip.prefetch("stft2048_flatness", vocal_dev, det_hop)
-    if floor_db is not None:                                                             # finalize_cut_points: the vocal guard's lookup
+    if floor_db is not None and n >= guard_window_samples(sr):                           # finalize_cut_points: the vocal guard's lookup
         db = hip.prefetch("moving_meansq_db", vocal_dev, guard_window_samples(sr))
         hip.prefetch("next_leq_scan", db, float(floor_db))

@@ -196,8 +196,11 @@ extern "C" int ac_next_leq_scan(ac_ctx* ctx, const double* db, int64_t n, double
 // =================================================================================================
 // First argmin over k windows of a float64 series.  One workgroup per window.
 // =================================================================================================
+// np.argmin's rule: the first NaN if there is one, else the first minimum
 __device__ inline void argmin_combine(double& v, long long& i, double ov, long long oi) {
-    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+    const bool on = isnan(ov), vn = isnan(v);
+    const bool take = (on || vn) ? (on && (!vn || oi < i)) : (ov < v || (ov == v && oi < i));
+    if (take) { v = ov; i = oi; }
 }
 
 __device__ inline void block_argmin_256(double& v, long long& i, double* s_v, long long* s_i) {
@@ -313,11 +316,11 @@ __global__ __launch_bounds__(256) void k_quiet_guard_slow(const float* __restric
     const int seg = (int)(end - c);
     double v = INFINITY; long long bi = NQ_INF;
     if (seg <= win) {
-        // level = raw samples (can be negative -> log10 of a negative is NaN in the reference; keep IEEE behaviour)
+        // level = raw samples: a negative one gives log10 of a negative, NaN, and np.argmin returns the first NaN
         for (int i = threadIdx.x; i < seg; i += 256) {
             const double d = 20.0 * log10((double)x[c + i] + 1e-12);
             if (i == 0) s_db0 = d;
-            if (d < v) { v = d; bi = i; }
+            if (d < v || (isnan(d) && !isnan(v))) { v = d; bi = i; }
         }
     } else {
         const int plen = seg + win - 1;
@@ -331,7 +334,16 @@ __global__ __launch_bounds__(256) void k_quiet_guard_slow(const float* __restric
         const int per = (seg + 255) / 256;      // windows per thread (<= QG_RUN_MAX by the host-side check)
         const int w0 = threadIdx.x * per;
         const int w1 = min(seg, w0 + per);
-        if (w0 < w1) {
+        if (w0 < w1 && w1 - w0 > win + 1) {
+            // a window shorter than the run: consecutive windows share no core, so each is summed on its own
+            for (int w = w0; w < w1; ++w) {
+                double acc = 0.0;
+                for (int j = w; j < w + win; ++j) acc += (double)s_sq[j] * inv;
+                const double d = 20.0 * log10(sqrt(acc + 1e-12) + 1e-12);
+                if (w == 0) s_db0 = d;
+                if (d < v) { v = d; bi = w; }
+            }
+        } else if (w0 < w1) {
             // windows [w, w+win) for w in [w0, w1): common core [w1-1, w0+win)
             // the additions stay one dependent float64 chain in index order (bit-identical sums); only the LDS reads are taken eight
             // at a time in front of it - one read, one wait, one add per iteration left the ~3 500-term chain latency-bound on LDS
@@ -407,6 +419,17 @@ __device__ void seg_env_argmin(const float* __restrict__ x, int64_t a, int m, in
         const int o0 = tile + (int)threadIdx.x * PC_RUN;
         const int o1 = min(out_len, o0 + PC_RUN);
         if (o0 >= o1) continue;
+        if (o1 - o0 > W + 1) {
+            // a window shorter than the run: consecutive windows share no core, so each is summed on its own (W <= 14)
+            for (int i = o0; i < o1; ++i) {
+                double acc = 0.0;
+                for (int j = max(i + off - W + 1, 0); j <= min(i + off, m - 1); ++j) { const float s = x[a + j]; acc += (double)(s * s); }
+                const float env = sqrtf(fmaxf((float)(acc * (double)invf), 1e-12f));
+                const double e = (double)env;
+                if (e < best) { best = e; best_i = i; }
+            }
+            continue;
+        }
         // samples common to every window of the run: j in [o1-1+off-W+1, o0+off]
         const int core_lo = o1 - 1 + off - W + 1, core_hi = o0 + off;
         // one dependent float64 chain in index order (bit-identical sums); the loads of eight terms are issued together in front of it
@@ -507,8 +530,10 @@ __global__ __launch_bounds__(256) void k_pause_cut(const float* __restrict__ x, 
         }
     }
     if (threadIdx.x == 0) {              // aux_out[2 q] (zeros in the segment) was accumulated by k_pause_argmin
+        // a pause shorter than `win` can put the first cut up to win - 1 samples past b, so past the track end when b is near n;
+        // the look-ahead is then empty and the cut stays there: the host reads cut >= n as "no sample at the cut"
         cut_out[q] = cut;
-        aux_out[2 * q + 1] = (x[cut] != 0.0f) ? 1 : 0;
+        aux_out[2 * q + 1] = (cut < n && x[cut] != 0.0f) ? 1 : 0;
     }
     (void)s_cut; (void)s_zero;
 }

@@ -122,9 +122,18 @@ class _Wave:
         self.lookup: Optional[QuietGuardLookup] = None
 
     def prepare_lookup(self, window_ms: float, floor_db: float) -> QuietGuardLookup:
-        """reference `_prepare_quiet_lookup` (`:161-181`)."""
+        """reference `_prepare_quiet_lookup` (`:161-181`).
+
+        A wave shorter than the window gets the reference's lookup exactly: `np.convolve` then swaps its operands and its 'same'
+        output has `win` values (a different centring from the kernel's `n`), and the fast guard clips to that length.  Such a
+        wave is shorter than 8192 samples, so numpy on the host serves it."""
         win = max(1, int(round(window_ms / 1000.0 * self.sr)))
-        db = self.hip.moving_meansq_db(self.dev, win)
+        if self.n < win:
+            sq = np.square(self.dev.cpu().numpy().astype(np.float64))
+            ms = np.convolve(sq, np.ones(win, dtype=np.float64) / float(win), mode="same")
+            db = self.hip.to_device(20.0 * np.log10(np.sqrt(ms + _EPS) + _EPS))
+        else:
+            db = self.hip.moving_meansq_db(self.dev, win)
         nq = self.hip.next_leq_scan(db, floor_db)
         self.lookup = QuietGuardLookup(db, nq, floor_db)
         return self.lookup
@@ -158,8 +167,9 @@ class _Wave:
         shift = max(1, int(round(max_shift_ms / 1000.0 * sr)))
         moved = np.zeros(len(times), dtype=bool)
         if use_lookup and self.lookup is not None:
-            idx = np.array([int(np.clip(int(round(t * sr)), 0, n - 1)) for t in times], dtype=np.int64)
-            ln = np.minimum(n, idx + shift) - idx
+            nl = int(self.lookup.rms_db.numel())          # n, or the window length for a wave shorter than the window
+            idx = np.array([int(np.clip(int(round(t * sr)), 0, nl - 1)) for t in times], dtype=np.int64)
+            ln = np.minimum(nl, idx + shift) - idx
             arg, val = self.hip.window_argmin(self.lookup.rms_db, idx, ln)
             for q in range(len(times)):
                 if ln[q] <= 0:

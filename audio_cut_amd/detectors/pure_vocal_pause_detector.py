@@ -641,7 +641,14 @@ class PureVocalPauseDetector:
         return out
 
     def _calculate_precise_cut_points(self, pauses: List[PureVocalPause], vocal_dev) -> List[PureVocalPause]:
-        """`:1020-1094` — one `ac_pause_cut_points` launch for all pauses."""
+        """`:1020-1094` — one `ac_pause_cut_points` launch for all pauses.
+
+        A pause shorter than the RMS window can put its cut up to `win - 1` samples past its end (`np.convolve` swaps its
+        operands and the 'same' output then has `win` values).  For a pause that ends within that distance of the track end the
+        cut can land at or past the last sample, where the look-ahead is empty.  The reference keeps such a cut when the pause's
+        percentile floor is zero; when the floor is positive it indexes `vocal[cut]` past the end and raises `IndexError`.  This
+        build keeps the cut in the first case and, in the second, takes the reference's own fallback: the pause midpoint, grade B.
+        """
         sr = self.sample_rate
         n = int(vocal_dev.numel())
         win = max(1, int(float(get_config("vocal_pause_splitting.local_rms_window_ms", 25)) / 1000.0 * sr))
@@ -669,12 +676,15 @@ class PureVocalPauseDetector:
             lo_i = int(math.floor(pos)); frac = pos - lo_i
             floor_positive = (zeros <= lo_i) or (frac > 0.0 and zeros <= lo_i + 1 and lo_i + 1 < m)
             fallback = False
-            if allow == 0.0:
+            if allow != 0.0:
+                floor_val = self._segment_percentile(vocal_dev, int(a[i]), int(b[i]), pct)
+                floor_positive = floor_val > 0.0
+            if c >= n:
+                exceeds = True                              # no sample at the cut: see the docstring
+            elif allow == 0.0:
                 exceeds = nonzero_at_cut                    # |x[cut]| > floor * 0.0
             else:
-                floor_val = self._segment_percentile(vocal_dev, int(a[i]), int(b[i]), pct)
                 exceeds = abs(float(vocal_dev[c].item())) > floor_val * allow
-                floor_positive = floor_val > 0.0
             if floor_positive and exceeds:
                 c = int(a[i]) + m // 2
                 fallback = True

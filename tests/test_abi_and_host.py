@@ -370,12 +370,12 @@ EXPORT_TESTS = {
     "ac_onset_strength": "test_kernels_gpu::test_onset_strength",
     "ac_tempogram_reduce": "test_kernels_gpu::test_tempogram_reduce",
     "ac_yin_f0": "test_kernels_gpu::test_yin_f0_autocorrelation_kernel",
-    "ac_moving_meansq_db_f64": "test_kernels_gpu::test_moving_meansq_db_and_next_leq",
-    "ac_next_leq_scan": "test_kernels_gpu::test_moving_meansq_db_and_next_leq",
-    "ac_window_argmin_f64": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
-    "ac_zero_cross_nearest": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
-    "ac_quiet_guard_slow": "test_kernels_gpu::test_window_argmin_zero_cross_and_slow_guard",
-    "ac_pause_cut_points": "test_kernels_gpu::test_pause_cut_points",
+    "ac_moving_meansq_db_f64": "test_cut_refine_edges_gpu::test_moving_meansq_db_edges",
+    "ac_next_leq_scan": "test_cut_refine_edges_gpu::test_next_leq_scan_edges",
+    "ac_window_argmin_f64": "test_cut_refine_edges_gpu::test_window_argmin_edges",
+    "ac_zero_cross_nearest": "test_cut_refine_edges_gpu::test_zero_cross_nearest_edges",
+    "ac_quiet_guard_slow": "test_cut_refine_edges_gpu::test_quiet_guard_slow_edges",
+    "ac_pause_cut_points": "test_cut_refine_edges_gpu::test_pause_cut_points_edges",
     "ac_mdx_stft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
     "ac_mdx_istft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
     "ac_mdx_assemble_ola": "test_kernels_gpu::test_mdx_stft_istft_assemble",
