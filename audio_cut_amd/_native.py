@@ -43,6 +43,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so ABI version mismatch")
     if lib.ac_stereo_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so stereo ABI version mismatch")
+    if lib.ac_onset_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so onset ABI version mismatch")
     _lib = lib
     return lib
 
@@ -114,8 +116,16 @@ STEREO_SIGNATURES = {
 }
 
 
+# include/audiocut_hip_onset.h: the `librosa_onset` mode's reductions, exported by the same library and versioned on their own
+ONSET_SIGNATURES = {
+    "ac_onset_abi_version": (C.c_int, []),
+    "ac_bar_energy_silence": (C.c_int, [_P, _P, _I64, _P, _P, _I, C.c_double, _P, _P, _P]),
+    "ac_segment_pair_energy": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I, _P, _P]),
+}
+
+
 def _declare(lib: C.CDLL) -> None:
-    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -473,6 +483,50 @@ class Context:
         for p in range(16):                       # fixed order: deterministic
             total += parts[:, p]
         return total, pk.cpu().numpy().max(axis=1)
+
+    # -- bar-aligned smart segmentation (include/audiocut_hip_onset.h) ---------------------------------
+    def bar_energy_silence(self, rms: torch.Tensor, bar_lo: np.ndarray, bar_hi: np.ndarray, threshold_db: float):
+        """(mean of rms[lo:hi] per bar in float64 - 0.0 for an empty range -, `20 log10(rms + 1e-10) < threshold_db` per frame as
+        bool), host arrays.  One staged upload (the ranges), one launch, one download (means and flags share a buffer)."""
+        self._chk_f32(rms)
+        lo = np.asarray(bar_lo, dtype=np.int64); hi = np.asarray(bar_hi, dtype=np.int64)
+        nf, nb = int(rms.numel()), int(lo.size)
+        if lo.shape != hi.shape or lo.ndim != 1 or nb == 0 or nf == 0:
+            raise ValueError("bar_lo / bar_hi must be equally long, non-empty 1-D sequences and rms non-empty")
+        if np.any(lo < 0) or np.any(hi < 0) or np.any(lo > nf) or np.any(hi > nf):       # hi <= lo is allowed: an empty bar
+            raise ValueError("bar ranges must lie inside the RMS series")
+        ranges = self.to_device(np.stack([lo, hi]))
+        # [n_bars float64 | n_frames uint8]: the float64 part sits at offset 0 of a fresh allocation (torch aligns those to 256+ bytes)
+        out = torch.empty(8 * nb + nf, dtype=torch.uint8, device=self.device)
+        _check(self.lib.ac_bar_energy_silence(self._h, _ptr(rms), nf, ranges.data_ptr(), ranges.data_ptr() + 8 * nb, nb,
+                                              float(threshold_db), out.data_ptr(), out.data_ptr() + 8 * nb, _stream()))
+        host = out.cpu().numpy()
+        return host[: 8 * nb].view(np.float64).copy(), host[8 * nb:].astype(bool)
+
+    def segment_pair_energy(self, vocal: torch.Tensor, inst: Optional[torch.Tensor], seg_start: np.ndarray, seg_end: np.ndarray):
+        """(sum of squares of vocal[a:b], of inst[a:b]) per segment as float64 host arrays, both stems in one launch; the
+        per-stem sums are `segment_sumsq_peak`'s bits.  `inst` None: its sums are zeros."""
+        self._chk_f32(vocal)
+        n = int(vocal.numel())
+        if inst is not None:
+            self._chk_f32(inst)
+            if inst.numel() != n:
+                raise NativeError("segment_pair_energy: the stems differ in length")
+        a = np.asarray(seg_start, dtype=np.int64); b = np.asarray(seg_end, dtype=np.int64)
+        k = int(a.size)
+        if a.shape != b.shape or a.ndim != 1 or k == 0:
+            raise ValueError("seg_start / seg_end must be equally long, non-empty 1-D sequences")
+        if np.any(a < 0) or np.any(b > n) or np.any(b < a):
+            raise ValueError("segments must lie inside the stems")
+        ranges = self.to_device(np.stack([a, b]))
+        parts_dev = torch.empty((k, 2, 16), dtype=torch.float64, device=self.device)
+        _check(self.lib.ac_segment_pair_energy(self._h, _ptr(vocal), _ptr(inst), n, ranges.data_ptr(), ranges.data_ptr() + 8 * k, k,
+                                               _ptr(parts_dev), _stream()))
+        parts = parts_dev.cpu().numpy()
+        total = np.zeros((k, 2), dtype=np.float64)
+        for p in range(16):                       # fixed order: deterministic
+            total += parts[:, :, p]
+        return total[:, 0].copy(), total[:, 1].copy()
 
     def local_valley(self, x: torch.Tensor, centers: np.ndarray, radius: int, win: int):
         """(orig_db, min_db, min_idx) per boundary, host arrays (see ac_local_valley)."""

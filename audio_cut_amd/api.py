@@ -2,7 +2,8 @@
 (`src/audio_cut/api.py:31-45`): load -> (resample) -> separate -> detect -> finalize -> boundary policy -> export ->
 SegmentManifest.
 
-Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`.
+Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, and `librosa_onset`
+(bar-aligned smart segmentation: mix segments by default, vocal segments on request, no full stems).
 Loader: PCM WAV / .npy, channel mean like `librosa.load(mono=True)`; a file whose rate differs from `audio.sample_rate`
 is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
@@ -199,8 +200,16 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
             audio_dev = hip.resample_poly(hip.to_device(audio), sr, file_sr)     # e.g. 48 kHz -> 44.1 kHz = up 147 / down 160
             audio = audio_dev.cpu().numpy()
     res = splitter.split_track(audio, mode=mode, audio_dev=audio_dev)
+    if not res.get("success", True):                    # `split_audio_seamlessly`'s failure result (`:231-233`): nothing is written
+        return {"success": False, "error": res.get("error"), "input_file": str(in_path), "mode": mode,
+                "timings": res.get("timings", {}), "processing_time": time.time() - t_start}
+    smart = mode == "librosa_onset"
     single = bool(res.get("single_segment"))            # `_create_single_segment_result`: only the mix, no duration tag
-    plan = _normalize_export_plan(export_types) if (export_types or not single) else ["mix_segments"]
+    if smart:       # `:1291-1322`: the mix segments by default; of the other kinds only the vocal segments are written in this mode
+        plan = [k for k in _normalize_export_plan(export_types) if k in ("mix_segments", "vocal_segments")] if export_types \
+            else ["mix_segments"]
+    else:
+        plan = _normalize_export_plan(export_types) if (export_types or not single) else ["mix_segments"]
     cuts = [int(c) for c in res.get("cuts_samples", res["sample_boundaries"])]
     spans = [tuple(sp) for sp in res.get("segment_spans", list(zip(cuts[:-1], cuts[1:])))]
     flags = list(res.get("segment_vocal_flags", [True] * len(spans)))
@@ -231,7 +240,7 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         exp.full_instrumental_file = exporter.export_full_track(inst_pk, out_dir / f"{in_path.stem}_{mode}_instrumental_{np.shape(inst)[-1] / float(sr):.1f}")
         exp.saved_files.append(exp.full_instrumental_file)
     out: Dict[str, Any] = {
-        "success": True, "mode": mode, "method": f"pure_vocal_split_{mode}", "input_file": str(in_path), "output_dir": str(out_dir),
+        "success": True, "mode": mode, "method": res.get("method", f"pure_vocal_split_{mode}"), "input_file": str(in_path), "output_dir": str(out_dir),
         "sample_rate": sr, "guard_boundaries_samples": [int(b) for b in res["sample_boundaries"]],
         "cut_points_samples": cuts, "cut_points_sec": [c / float(sr) for c in cuts],
         "num_segments": len(spans), "segment_durations": durations, "segment_vocal_flags": flags,
@@ -251,6 +260,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     }
     if res.get("note"):
         out["note"] = res["note"]
+    if smart:       # `:1341-1347`, and the bar analysis behind the cuts
+        for key in ("use_vocal_preprocessing", "bpm", "bar_duration_s", "density", "silence_boundaries", "bar_energies", "bar_types"):
+            out[key] = res.get(key)
     if res.get("boundary_detection") is not None:
         out["boundary_detection"] = res["boundary_detection"]
         out["lyrics_alignment"] = res.get("lyrics_alignment")

@@ -9,6 +9,7 @@ restricted to the keys SURVEY.md Appendix A lists for the separate+detect path.
 from __future__ import annotations
 
 import copy
+import os
 from typing import Any, Dict
 
 DEFAULTS: Dict[str, Any] = {
@@ -83,6 +84,15 @@ DEFAULTS: Dict[str, Any] = {
         "enable": True, "hard_min_s": 2.0, "hard_max_s": 18.0, "target_min_s": 5.0, "target_max_s": 12.0,
         "vocal_risk_weight": 0.25, "beat_conflict_weight": 0.15, "max_candidates_per_second": 2.0, "rescue_enabled": True,
     },
+    # mode `librosa_onset` (`expert.yaml:129-144`)
+    "librosa_onset": {
+        "use_vocal_separation": True,
+        "silence": {"threshold_db": -40, "min_duration": 0.3},
+        "density": "low",
+        "density_custom": {"enable": False, "verse_bars": 4, "chorus_bars": 2},
+        "energy_analysis": {"hop_length": 512, "chorus_percentile": 60, "chorus_peak_percentile": 80},
+        "beat": {"time_signature": 4},
+    },
 }
 
 _runtime: Dict[str, Any] = {}
@@ -144,6 +154,36 @@ def get_config(path: str, default: Any = None) -> Any:
             node = node.setdefault(p, {})
         node[parts[-1]] = copy.deepcopy(v)
     return value
+
+
+def _env_override(value: Any, env_key: str, convert) -> Any:
+    """`_get_with_env_override` (`config_manager.py:582-602`): the environment wins; a value that does not convert is ignored."""
+    raw = os.environ.get(env_key)
+    if raw is None:
+        return value
+    try:
+        return convert(raw)
+    except (ValueError, TypeError):
+        return value
+
+
+def get_librosa_onset_config() -> Dict[str, Any]:
+    """`get_librosa_onset_config` (`config_manager.py:527-579`): the `librosa_onset` section with the reference's literal
+    defaults for absent keys, and the `AUDIOCUT_*` environment overrides on top of four of them."""
+    base = get_config("librosa_onset", {}) or {}
+    silence = base.get("silence", {})
+    return {
+        "use_vocal_separation": _env_override(base.get("use_vocal_separation", True), "AUDIOCUT_LIBROSA_USE_VOCAL",
+                                              lambda x: x.lower() == "true"),
+        "silence": {
+            "threshold_db": _env_override(silence.get("threshold_db", -40), "AUDIOCUT_SILENCE_THRESHOLD_DB", float),
+            "min_duration": _env_override(silence.get("min_duration", 0.3), "AUDIOCUT_SILENCE_MIN_DURATION", float),
+        },
+        "density": _env_override(base.get("density", "medium"), "AUDIOCUT_DENSITY", str),
+        "density_custom": base.get("density_custom", {"enable": False, "verse_bars": 4, "chorus_bars": 2}),
+        "energy_analysis": base.get("energy_analysis", {"hop_length": 512, "chorus_percentile": 60, "chorus_peak_percentile": 80}),
+        "beat": base.get("beat", {"time_signature": 4}),
+    }
 
 
 def set_runtime_config(overrides: Dict[str, Any]) -> None:

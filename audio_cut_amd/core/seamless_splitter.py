@@ -51,7 +51,7 @@ PRECISION_GUARD_P95_MS = 220.0
 
 
 class SeamlessSplitter:
-    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr")
+    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr", "librosa_onset")
 
     def __init__(self, sample_rate: int = 44100, *, separator: Optional[EnhancedVocalSeparator] = None,
                  device: Optional[str] = None) -> None:
@@ -87,6 +87,10 @@ class SeamlessSplitter:
         sr = self.sample_rate
         if original_audio is None or len(original_audio) == 0 or np.shape(original_audio)[-1] == 0:
             raise ValueError("split_track needs a non-empty mono track")
+        if mode == "librosa_onset":
+            if separation_gate is not None or unet_stream is not None:
+                raise ValueError("librosa_onset tracks are split one at a time (no separation gate / U-Net stream)")
+            return self._split_librosa_onset(original_audio, audio_dev)
         stereo = np.ndim(original_audio) == 2
         t0 = time.perf_counter()
         sep: SeparationResult = self.separator.separate_for_detection(original_audio, gpu_context=None, audio_dev=audio_dev,
@@ -199,6 +203,117 @@ class SeamlessSplitter:
                 "avg_guard_only_shift_ms": mean_pos(total), "avg_vocal_guard_shift_ms": mean_pos(vocal),
                 "avg_mix_guard_shift_ms": mean_pos(total - vocal), "p95_shift_ms": float(np.percentile(np.abs(total), 95.0)),
                 "count": int(total.size)}
+
+    # ---- mode `librosa_onset`: bar-aligned smart segmentation (reference `seamless_splitter.py:1038-1349`) -----------
+    def _split_librosa_onset(self, original_audio: np.ndarray, audio_dev=None) -> Dict:
+        """Steps 0-7 and 9 of `_process_librosa_onset_split` on an in-memory track: (separation) -> tempo -> bar grid -> mean RMS
+        per bar and silent frames (`ac_bar_energy_silence`) -> chorus / verse bars -> density-controlled bar cuts with forced
+        cuts at silences -> sample points -> human / music labels from both stems (`ac_segment_pair_energy`).
+        The mix is read once for the RMS(2048, hop) series, which is queued before the tempo is known; the tempo is the only
+        host decision between that pass and the bar kernel.  A track whose tempo comes out 0 makes the reference divide by
+        zero and report `{'success': False}` (`:1097`, `:231-233`): so does this."""
+        from ..analysis.rhythm import beat_track_from_device
+        from ..config import get_librosa_onset_config
+        from ..cutting import smart_segment as SS
+        import torch
+        sr = self.sample_rate
+        lo_config = get_librosa_onset_config()
+        use_vocal = bool(lo_config["use_vocal_separation"])
+        stereo = np.ndim(original_audio) == 2
+        n = int(np.shape(original_audio)[-1])
+        duration = n / float(sr)
+        t0 = time.perf_counter()
+        sep: Optional[SeparationResult] = None
+        if use_vocal:
+            sep = self.separator.separate_for_detection(original_audio, gpu_context=None, audio_dev=audio_dev)
+            state = dict(sep.device_state or {})
+            hip = state.get("hip") or self._context()
+        else:                                   # no U-Net: the track goes to the device for the analysis alone
+            hip = self._context()
+            track_dev = audio_dev if audio_dev is not None else hip.to_device(np.ascontiguousarray(original_audio, dtype=np.float32))
+            state = {"hip": hip, "mix": torch.add(track_dev[0], track_dev[1]).mul_(0.5) if stereo else track_dev}
+            if stereo:
+                state["mix_stereo"] = track_dev
+        mix_dev = state.get("mix")
+        if mix_dev is None:
+            mono = sep.mono_mix if stereo else original_audio
+            mix_dev = hip.to_device(np.ascontiguousarray(mono, dtype=np.float32))
+            state["mix"] = mix_dev
+        t_sep = time.perf_counter() - t0
+
+        # 3. features (`:1089-1165`)
+        t1 = time.perf_counter()
+        hop = int(lo_config["energy_analysis"].get("hop_length", 512))
+        time_signature = lo_config["beat"].get("time_signature", 4)
+        rms_dev = hip.frame_rms(mix_dev, 2048, hop)                        # the one pass over the mix, queued ahead of the tempo
+        _, mel = hip.stft2048_features(mix_dev, hop, want_flat=False, want_mel=True)
+        env_dev = hip.onset_strength(mel, hop, "median")                    # librosa.beat.beat_track's envelope
+        del mel
+        tempo, beats, _ = beat_track_from_device(hip, env_dev, sr, hop)
+        result: Dict = {"mode": "librosa_onset", "method": "smart_segment_v2", "use_vocal_preprocessing": use_vocal,
+                        "gpu_meta": dict(sep.gpu_meta or {}) if sep is not None else {},
+                        "separation_confidence": sep.separation_confidence if sep is not None else None,
+                        "backend_used": sep.backend_used if sep is not None else None, "device_state": state,
+                        "vocal_track": sep.vocal_track if sep is not None else None,
+                        "instrumental_track": sep.instrumental_track if sep is not None else None}
+        if stereo and sep is not None:
+            result.update({"vocal_track_stereo": sep.vocal_track_stereo, "instrumental_track_stereo": sep.instrumental_track_stereo,
+                           "mono_mix": sep.mono_mix})
+        try:
+            bar_duration = 60.0 / tempo * time_signature
+        except ZeroDivisionError as exc:
+            logger.error("split failed: %s", exc)
+            result.update({"success": False, "error": str(exc), "bpm": tempo})
+            return result
+        n_frames = int(rms_dev.numel())
+        rms_times = SS.rms_frame_times(n_frames, sr, hop)
+        bar_times = SS.bar_grid(duration, bar_duration)
+        bar_lo, bar_hi = SS.bar_frame_ranges(rms_times, bar_times)
+        silence_cfg = lo_config["silence"]
+        means, silent = hip.bar_energy_silence(rms_dev, bar_lo, bar_hi, float(silence_cfg["threshold_db"]))
+        bar_energies = [float(e) for e in means]
+        energy_cfg = lo_config["energy_analysis"]
+        bar_types, thr_chorus, thr_peak = SS.classify_bars(bar_energies, energy_cfg.get("chorus_percentile", 60),
+                                                           energy_cfg.get("chorus_peak_percentile", 80))
+        silences = SS.silence_boundaries(silent, rms_times, duration, silence_cfg["min_duration"])
+
+        # 4.-6. density, cut times, sample points (`:1167-1250`)
+        density_cfg = SS.density_config(lo_config)
+        cut_times = SS.plan_bar_cuts(bar_times, bar_types, silences, density_cfg, duration,
+                                     float(get_config("segment_layout.soft_min_s", 2.0)))
+        cuts = SS.to_sample_points(cut_times, sr, n)
+        t_det = time.perf_counter() - t1
+
+        # 7. human / music labels (`:1252-1273`)
+        t2 = time.perf_counter()
+        vocal_dev = state.get("vocal") if (sep is not None and sep.vocal_track is not None) else None
+        if sep is not None and sep.vocal_track is not None and vocal_dev is None:
+            vocal_dev = hip.to_device(np.ascontiguousarray(sep.vocal_track, dtype=np.float32))
+        vocal_ss = inst_ss = None
+        if vocal_dev is not None:
+            inst_dev = None
+            if sep.instrumental_track is not None:
+                inst_dev = state.get("instrumental")
+                if inst_dev is None:
+                    inst_dev = hip.to_device(np.ascontiguousarray(sep.instrumental_track, dtype=np.float32))
+            vocal_ss, inst_ss = hip.segment_pair_energy(vocal_dev, inst_dev, cuts[:-1], cuts[1:])
+            if inst_dev is None:
+                inst_ss = None
+        flags = SS.label_segments(vocal_ss, inst_ss, cuts)
+        # `:1282`: the sample-level split glues a slice under 10 ms to its neighbour.  As in the reference the cut points then
+        # keep the glued point while flags and spans do not; the soft_min_s merge above leaves no such slice unless it is
+        # configured under 10 ms.
+        spans, merged_flags = self._sample_level_spans(n, cuts, flags)
+        spans = list(spans)
+        t_fin = time.perf_counter() - t2
+        result.update({"success": True, "bpm": tempo, "bar_duration_s": bar_duration, "density": lo_config["density"],
+                       "silence_boundaries": silences, "bar_energies": bar_energies, "bar_types": bar_types,
+                       "sample_boundaries": list(cuts), "cuts_samples": list(cuts),
+                       "cuts_sec": [c / float(sr) for c in cuts], "segment_vocal_flags": list(merged_flags or []),
+                       "segment_spans": spans, "segment_durations": [(hi - lo) / float(sr) for lo, hi in spans],
+                       "segment_layout_applied": False, "precision_guard_ok": True,
+                       "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": t_fin}})
+        return result
 
     # ------------------------------------------------------------------------------------------
     def _single_segment_fields(self, vocal_track: np.ndarray, n_samples: int, vocal_dev=None) -> Dict:
@@ -387,8 +502,13 @@ class SeamlessSplitter:
                                debug_entries: Optional[List[Dict]] = None):
         """`:2006-2144`: slices between consecutive cut points; a slice shorter than 10 ms is glued to the next one (a
         trailing one to the previous).  Slices are views of `audio` unless a merge forces a copy."""
+        spans, flags = self._sample_level_spans(len(audio), final_cut_points, segment_flags)
+        return [audio[lo:hi] for lo, hi in spans], flags, None
+
+    def _sample_level_spans(self, n: int, final_cut_points: List[int], segment_flags: Optional[List[bool]] = None):
+        """The spans `_split_at_sample_level` slices a track of `n` samples into, and their merged flags (None without
+        `segment_flags`); kept in `_last_segment_spans` too."""
         keep = max(1, int(0.01 * self.sample_rate))
-        n = len(audio)
         spans: List[List[int]] = []
         flags: Optional[List[bool]] = [] if segment_flags is not None else None
         pending: Optional[List[int]] = None
@@ -417,7 +537,7 @@ class SeamlessSplitter:
                 if flags is not None:
                     flags.append(bool(pending_flag))
         self._last_segment_spans = [tuple(sp) for sp in spans]
-        return [audio[lo:hi] for lo, hi in spans], flags, None
+        return self._last_segment_spans, flags
 
     def _apply_boundary_policy(self, bounds: List[int], vocal_track: np.ndarray, n_samples: int,
                                cache: Optional[TrackFeatureCache], *, vocal_dev=None) -> Dict:
