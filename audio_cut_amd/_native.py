@@ -45,6 +45,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so stereo ABI version mismatch")
     if lib.ac_onset_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so onset ABI version mismatch")
+    if lib.ac_beat_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so beat ABI version mismatch")
     _lib = lib
     return lib
 
@@ -123,9 +125,17 @@ ONSET_SIGNATURES = {
     "ac_segment_pair_energy": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I, _P, _P]),
 }
 
+# include/audiocut_hip_beat.h: the beat / bar analysis layer's spectral series and per-bar means, exported by the same library and
+# versioned on their own
+BEAT_SIGNATURES = {
+    "ac_beat_abi_version": (C.c_int, []),
+    "ac_stft2048_centroid_bandwidth": (C.c_int, [_P, _P, _I64, _I, C.c_double, _P, _P, _I64, _P]),
+    "ac_bar_means3": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I, _P, _P]),
+}
+
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -527,6 +537,46 @@ class Context:
         for p in range(16):                       # fixed order: deterministic
             total += parts[:, :, p]
         return total[:, 0].copy(), total[:, 1].copy()
+
+    # -- beat / bar analysis (include/audiocut_hip_beat.h) ---------------------------------------------
+    def stft2048_centroid_bandwidth(self, x: torch.Tensor, sr: int, hop: int):
+        """(spectral centroid, spectral bandwidth) per centred 2048-sample frame, float64 device tensors [1 + n // hop]:
+        librosa.feature.spectral_centroid / spectral_bandwidth at their defaults.  The centroid has `stft2048_spectral`'s bits."""
+        self._chk_f32(x)
+        hit = self._pf_take("stft2048_centroid_bandwidth", x, sr, int(hop))
+        if hit is not None:
+            return hit
+        n = x.numel()
+        if n == 0 or hop <= 0:
+            raise ValueError("stft2048_centroid_bandwidth needs a non-empty signal and a positive hop")
+        nf = 1 + n // hop
+        out = torch.empty((2, nf), dtype=torch.float64, device=self.device)
+        _check(self.lib.ac_stft2048_centroid_bandwidth(self._h, _ptr(x), n, int(hop), float(sr), out.data_ptr(), out.data_ptr() + 8 * nf,
+                                                       nf, _stream()))
+        return out[0], out[1]
+
+    def bar_means3(self, rms: torch.Tensor, centroid: torch.Tensor, bandwidth: torch.Tensor, bar_lo: np.ndarray,
+                   bar_hi: np.ndarray) -> np.ndarray:
+        """Means of rms / centroid / bandwidth over the frames [bar_lo[b], bar_hi[b]) of every bar -> float64 host array
+        [3, n_bars], zeros for an empty range.  One staged upload (the ranges), one launch, one download."""
+        self._chk_f32(rms)
+        for t in (centroid, bandwidth):
+            if t.dtype != torch.float64 or t.device != self.device or t.dim() != 1 or not t.is_contiguous():
+                raise NativeError("expected contiguous 1-D float64 tensors on the context's device")
+        nf = int(rms.numel())
+        if int(centroid.numel()) != nf or int(bandwidth.numel()) != nf:
+            raise ValueError("bar_means3: the three series must have the same number of frames")
+        lo = np.asarray(bar_lo, dtype=np.int64); hi = np.asarray(bar_hi, dtype=np.int64)
+        nb = int(lo.size)
+        if lo.shape != hi.shape or lo.ndim != 1 or nb == 0 or nf == 0:
+            raise ValueError("bar_lo / bar_hi must be equally long, non-empty 1-D sequences and the series non-empty")
+        if np.any(lo < 0) or np.any(hi < 0) or np.any(lo > nf) or np.any(hi > nf):       # hi <= lo is allowed: an empty bar
+            raise ValueError("bar ranges must lie inside the series")
+        ranges = self.to_device(np.stack([lo, hi]))
+        out = torch.empty((3, nb), dtype=torch.float64, device=self.device)
+        _check(self.lib.ac_bar_means3(self._h, _ptr(rms), nf, _ptr(centroid), _ptr(bandwidth), nf, ranges.data_ptr(),
+                                      ranges.data_ptr() + 8 * nb, nb, _ptr(out), _stream()))
+        return out.cpu().numpy()
 
     def local_valley(self, x: torch.Tensor, centers: np.ndarray, radius: int, win: int):
         """(orig_db, min_db, min_idx) per boundary, host arrays (see ac_local_valley)."""

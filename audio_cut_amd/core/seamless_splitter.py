@@ -21,6 +21,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .. import _native
+from ..analysis.beat_analyzer import BeatAnalyzer, queue_frame_series
+from ..analysis.chorus_regions import detect_chorus_regions
 from ..analysis.features_cache import TrackFeatureCache, build_feature_cache
 from ..config import get_config
 from ..cutting.refine import CutContext, CutPoint, CutRefineResult, finalize_cut_points
@@ -62,6 +64,7 @@ class SeamlessSplitter:
         self.pure_vocal_detector = PureVocalPauseDetector(sample_rate, ctx=self._hip)
         from .vocal_phrase_boundary_detector import VocalPhraseBoundaryDetector
         self.vpbd_detector = VocalPhraseBoundaryDetector(sample_rate)
+        self.beat_analyzer = BeatAnalyzer(sample_rate, ctx=self._hip)
         self._last_guard_adjustments_raw: list = []
         self._last_suppressed_cut_points: list = []
 
@@ -72,7 +75,7 @@ class SeamlessSplitter:
 
     # ------------------------------------------------------------------------------------------
     def split_track(self, original_audio: np.ndarray, mode: str = "v2.2_mdd", *, audio_dev=None, separation_gate=None,
-                    unet_stream=None) -> Dict:
+                    unet_stream=None, beat_analysis: bool = False) -> Dict:
         """Steps 2-9 of SURVEY.md §3.1 on an in-memory mono float32 track at `sample_rate`.
         `separation_gate` (a lock shared by the workers of a `batch.TrackPipeline`) and `unet_stream` (the pipeline's one U-Net
         stream): with both, this track's separation is queued on that stream under the lock and the lock is released as soon as it is
@@ -81,7 +84,10 @@ class SeamlessSplitter:
         released before the host-bound tail.
         A planar stereo (2, N) track (and a [2, N] `audio_dev`) is separated on true L/R; detection, guards and boundaries run on its
         mono mix (L + R) * 0.5 exactly as on a mono track of those samples, and the result adds `vocal_track_stereo` /
-        `instrumental_track_stereo` ([2, N]) and `mono_mix`.  Stereo tracks are not taken with a gate or U-Net stream."""
+        `instrumental_track_stereo` ([2, N]) and `mono_mix`.  Stereo tracks are not taken with a gate or U-Net stream.
+        `beat_analysis=True` adds a `"beat_analysis"` block (tempo, bars, per-bar energy / centroid / bandwidth, high-energy and
+        chorus bars: `_beat_analysis_block`) to the result of every mode that builds a feature cache - all but `librosa_onset`,
+        which reports its own bar analysis.  Off, nothing is launched for it."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
         sr = self.sample_rate
@@ -103,6 +109,7 @@ class SeamlessSplitter:
         cache: Optional[TrackFeatureCache] = sep.feature_cache
         if cache is None:
             cache = build_feature_cache(original_audio, vocal_track, sr, ctx=self._context(), mix_dev=state.get("mix"))
+        beat_pending = self._beat_analysis_queue(original_audio, state) if beat_analysis else None
         markers = sep.quality_metrics or {}
         marker_times = [float(t) for t in markers.get("vocal_presence_cut_points_sec", []) if t is not None]
 
@@ -132,6 +139,7 @@ class SeamlessSplitter:
                 result.update({"sample_boundaries": [0, len(original_audio)], "note": "no_vpbd_candidates",
                                "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": 0.0}})
                 result.update(self._single_segment_fields(vocal_track, len(original_audio), state.get("vocal")))
+                self._beat_analysis_block(beat_pending, original_audio, cache, result)
                 return result
             t2 = time.perf_counter()
         else:
@@ -144,6 +152,7 @@ class SeamlessSplitter:
                 result.update({"sample_boundaries": [0, len(original_audio)], "note": "no_pause_candidates",
                                "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": 0.0}})
                 result.update(self._single_segment_fields(vocal_track, len(original_audio), state.get("vocal")))
+                self._beat_analysis_block(beat_pending, original_audio, cache, result)
                 return result
             t2 = time.perf_counter()
             cut_candidates = [(float(p.cut_point), float(p.confidence)) for p in pauses]
@@ -188,7 +197,48 @@ class SeamlessSplitter:
                        "precision_guard_ok": bool(stats["avg_shift_ms"] <= PRECISION_GUARD_AVG_MS and stats["p95_shift_ms"] <= PRECISION_GUARD_P95_MS),
                        "precision_guard_threshold_ms": {"avg": PRECISION_GUARD_AVG_MS, "p95": PRECISION_GUARD_P95_MS},
                        "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": t_fin}})
+        self._beat_analysis_block(beat_pending, original_audio, cache, result)
         return result
+
+    # ---- optional beat / bar analysis block (reference `audio_cut.analysis.beat_analyzer`, `chorus_regions`) -----------
+    def _beat_analysis_queue(self, mono_mix: np.ndarray, state: Dict):
+        """Queue the RMS and centroid / bandwidth passes over the resident mix on a stream of their own, right after the
+        separation: they run beside the detection tail, which is bound by the host, instead of in front of it."""
+        import torch
+        hip = state.get("hip") or self._context()
+        mix_dev = state.get("mix")
+        if mix_dev is None:
+            mix_dev = hip.to_device(np.ascontiguousarray(mono_mix, dtype=np.float32))
+        main = torch.cuda.current_stream()
+        side = torch.cuda.Stream(device=hip.device)
+        side.wait_stream(main)                                  # the mix is written on the main stream
+        with torch.cuda.stream(side):
+            series = queue_frame_series(hip, mix_dev, self.sample_rate, self.beat_analyzer.hop_length)
+            done = torch.cuda.Event()
+            done.record()
+        mix_dev.record_stream(side)
+        for t in series:
+            t.record_stream(main)                               # allocated on the side stream, read by `ac_bar_means3` on the main one
+        return hip, mix_dev, series, done
+
+    def _beat_analysis_block(self, pending, mono_mix: np.ndarray, cache: TrackFeatureCache, result: Dict) -> None:
+        """`result["beat_analysis"]`: `BeatAnalyzer.analyze` on the mix with the cache's beats and BPM, and the chorus bars of the
+        spectral-fusion `detect_chorus_regions` over its per-bar lists."""
+        if pending is None:
+            return
+        import torch
+        hip, mix_dev, series, done = pending
+        torch.cuda.current_stream().wait_event(done)
+        res = self.beat_analyzer.analyze(mono_mix, sr=self.sample_rate, feature_cache=cache, ctx=hip, audio_dev=mix_dev,
+                                         frame_series=series)
+        chorus = detect_chorus_regions(res.bar_energies, res.energy_threshold, bar_centroids=res.bar_spectral_centroids,
+                                       bar_bandwidths=res.bar_spectral_bandwidths)
+        result["beat_analysis"] = {"tempo": res.tempo, "bar_times": [float(t) for t in res.bar_times],
+                                   "bar_duration": res.bar_duration, "bar_energies": list(res.bar_energies),
+                                   "bar_spectral_centroids": list(res.bar_spectral_centroids),
+                                   "bar_spectral_bandwidths": list(res.bar_spectral_bandwidths),
+                                   "energy_threshold": res.energy_threshold, "high_energy_bars": sorted(res.high_energy_bars),
+                                   "chorus_bars": sorted(chorus)}
 
     @staticmethod
     def _guard_shift_stats(adjustments: Sequence) -> Dict[str, float]:

@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include "ac_common.h"
+#include "ac_fft2048.h"
 
 // =================================================================================================
 // Framed RMS.  One workgroup computes FPB consecutive frames from one LDS-resident span of the
@@ -117,41 +118,6 @@ extern "C" int ac_frame_rms_multi(ac_ctx* ctx, const float* x, int64_t n, int n_
 // the FFT and only then rounds to complex64) -> power -> flatness / mel-128.
 // One workgroup per frame; real FFT via a 1024-point complex Stockham radix-4 FFT in LDS.
 // =================================================================================================
-__device__ inline double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-
-// 1024-point complex forward FFT, 256 threads, 5 radix-4 Stockham passes; result in `a` (ping-pong with `b`).
-__device__ inline double2* fft1024_f64(double2* a, double2* b, const double2* __restrict__ tw2048) {
-    const int j = threadIdx.x;            // butterfly index, 0..255
-    int Ns = 1;
-#pragma unroll
-    for (int pass = 0; pass < 5; ++pass) {
-        const int k = j & (Ns - 1);
-        double2 v0 = a[j], v1 = a[j + 256], v2 = a[j + 512], v3 = a[j + 768];
-        // twiddle exp(-2*pi*i*k*m/(4*Ns)) = tw2048[k*m*(2048/(4*Ns))]
-        const int stride = 512 / Ns;      // 2048 / (4*Ns)
-        if (Ns > 1) {
-            v1 = cmul(v1, tw2048[k * stride]);
-            const int i2 = 2 * k * stride, i3 = 3 * k * stride;   // < 2048*3/4 ; tw table holds k < 1024: fold
-            double2 t2 = tw2048[i2 & 1023]; if (i2 & 1024) { t2.x = -t2.x; t2.y = -t2.y; }
-            double2 t3 = tw2048[i3 & 1023]; if (i3 & 1024) { t3.x = -t3.x; t3.y = -t3.y; }
-            v2 = cmul(v2, t2);
-            v3 = cmul(v3, t3);
-        }
-        // radix-4 butterfly (forward: -i rotation)
-        const double2 s02 = make_double2(v0.x + v2.x, v0.y + v2.y), d02 = make_double2(v0.x - v2.x, v0.y - v2.y);
-        const double2 s13 = make_double2(v1.x + v3.x, v1.y + v3.y), d13 = make_double2(v1.x - v3.x, v1.y - v3.y);
-        const int base = ((j - k) << 2) + k;
-        b[base] = make_double2(s02.x + s13.x, s02.y + s13.y);
-        b[base + Ns] = make_double2(d02.x + d13.y, d02.y - d13.x);
-        b[base + 2 * Ns] = make_double2(s02.x - s13.x, s02.y - s13.y);
-        b[base + 3 * Ns] = make_double2(d02.x - d13.y, d02.y + d13.x);
-        __syncthreads();
-        double2* t = a; a = b; b = t;
-        Ns <<= 2;
-    }
-    return a;
-}
-
 __global__ __launch_bounds__(256) void k_stft2048(const float* __restrict__ x, int64_t n, int hop,
                                                   const int64_t* __restrict__ frame_center,
                                                   const int64_t* __restrict__ frame_lo,
@@ -168,29 +134,11 @@ __global__ __launch_bounds__(256) void k_stft2048(const float* __restrict__ x, i
     const int64_t c = frame_center ? frame_center[f] : f * (int64_t)hop;
     const int64_t lo = frame_lo ? frame_lo[f] : 0;
     const int64_t hi = frame_hi ? frame_hi[f] : n;
-    const int64_t s0 = c - 1024;
-    // z[m] = w[2m] x[2m] + i w[2m+1] x[2m+1]
-    for (int m = threadIdx.x; m < 1024; m += 256) {
-        const int64_t g0 = s0 + 2 * m, g1 = g0 + 1;
-        const double a0 = (g0 >= lo && g0 < hi) ? (double)x[g0] : 0.0;
-        const double a1 = (g1 >= lo && g1 < hi) ? (double)x[g1] : 0.0;
-        s_a[m] = make_double2(a0 * hann[2 * m], a1 * hann[2 * m + 1]);
-    }
-    __syncthreads();
+    stft2048_load_frame(x, c - 1024, lo, hi, hann, s_a);
     const double2* Z = fft1024_f64(s_a, s_b, tw);
-    // untangle: X[k] = (Z[k] + conj(Z[N-k]))/2 - i W^k (Z[k] - conj(Z[N-k]))/2, N = 1024, W = exp(-2 pi i/2048)
     for (int k = threadIdx.x; k <= 1024; k += 256) {
-        const double2 zk = Z[k & 1023];
-        const double2 zn = Z[(1024 - k) & 1023];
-        const double2 e = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-        const double2 o = make_double2(0.5 * (zk.x - zn.x), 0.5 * (zk.y + zn.y));
-        double2 w = (k < 1024) ? tw[k] : make_double2(-1.0, 0.0);
-        // -i * w * o
-        const double2 wo = cmul(w, o);
-        const double re = e.x + wo.y, im = e.y - wo.x;
         // librosa stores complex64, then np.abs (hypotf) and **2 in float32
-        const float re32 = (float)re, im32 = (float)im;
-        const float mag = (float)sqrt((double)re32 * (double)re32 + (double)im32 * (double)im32);
+        const float mag = stft2048_mag_f32(stft2048_bin_c64(Z, tw, k));
         s_p[k] = mag * mag;
     }
     __syncthreads();
@@ -249,37 +197,11 @@ __global__ __launch_bounds__(256) void k_stft2048_spectral(const float* __restri
     __shared__ float s_m[1025];
     __shared__ double s_red[12];
     const int64_t f = blockIdx.x;
-    const int64_t s0 = f * (int64_t)hop - 1024;
-    for (int m = threadIdx.x; m < 1024; m += 256) {
-        const int64_t g0 = s0 + 2 * m, g1 = g0 + 1;
-        const double a0 = (g0 >= 0 && g0 < n) ? (double)x[g0] : 0.0;
-        const double a1 = (g1 >= 0 && g1 < n) ? (double)x[g1] : 0.0;
-        s_a[m] = make_double2(a0 * hann[2 * m], a1 * hann[2 * m + 1]);
-    }
-    __syncthreads();
+    stft2048_load_frame(x, f * (int64_t)hop - 1024, 0, n, hann, s_a);
     const double2* Z = fft1024_f64(s_a, s_b, tw);
-    for (int k = threadIdx.x; k <= 1024; k += 256) {
-        const double2 zk = Z[k & 1023];
-        const double2 zn = Z[(1024 - k) & 1023];
-        const double2 e = make_double2(0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y));
-        const double2 o = make_double2(0.5 * (zk.x - zn.x), 0.5 * (zk.y + zn.y));
-        double2 w = (k < 1024) ? tw[k] : make_double2(-1.0, 0.0);
-        const double2 wo = cmul(w, o);
-        const float re32 = (float)(e.x + wo.y), im32 = (float)(e.y - wo.x);     // complex64 storage, then np.abs
-        s_m[k] = (float)sqrt((double)re32 * (double)re32 + (double)im32 * (double)im32);
-    }
-    __syncthreads();
-    double tot = 0.0, low = 0.0;
-    for (int k = threadIdx.x; k <= 1024; k += 256) { const double v = (double)s_m[k]; tot += v; if (k < 1025 / 3) low += v; }
-    const double length = block_sum_f64_256(tot, s_red);
-    const double lowsum = block_sum_f64_256(low, s_red + 4);
-    const double len_eff = length < 1.17549435e-38 ? 1.0 : length;
-    double c = 0.0;
-    for (int k = threadIdx.x; k <= 1024; k += 256) {
-        const float sn = (float)((double)s_m[k] / len_eff);
-        c += ((double)k * sr / 2048.0) * (double)sn;
-    }
-    const double csum = block_sum_f64_256(c, s_red + 8);
+    stft2048_magnitudes(Z, tw, s_m);                                            // complex64 storage, then np.abs
+    double length, lowsum, len_eff;
+    const double csum = stft2048_centroid(s_m, sr, s_red, &length, &lowsum, &len_eff);
     if (threadIdx.x == 0) {
         centroid_out[f] = csum;
         const float lo32 = (float)lowsum, hi32 = (float)(length - lowsum);

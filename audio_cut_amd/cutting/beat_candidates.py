@@ -1,6 +1,6 @@
 """Weak beat-aligned candidates inside continuous high-energy bars — mirrors the reference's
-`src/audio_cut/cutting/beat_candidates.py:16-142` and the energy-only branch of
-`src/audio_cut/analysis/chorus_regions.py:15-99`.
+`src/audio_cut/cutting/beat_candidates.py:16-142`.  `detect_chorus_regions` is `analysis.chorus_regions`'s, re-exported
+here as the reference does; this path passes it no spectral lists, so it takes the energy branch.
 
 `vocal_cut_risk` (reference `:117-142`: window RMS / track peak) reads the vocal stem where it lives:
 on the GPU (`ac_sum_squares` over the +-80 ms window, `ac_abs_max`-free peak via the same reduction
@@ -8,37 +8,12 @@ helper) when a device copy is supplied, else from the host array with the refere
 """
 from __future__ import annotations
 
-from typing import Iterable, List, Optional, Set
+from typing import Iterable, List, Optional
 
 import numpy as np
 
+from ..analysis.chorus_regions import detect_chorus_regions
 from .cut_candidate import CandidateSource, CutCandidate
-
-
-def detect_chorus_regions(bar_energies: Iterable[float], energy_threshold: float, *, min_consecutive_bars: int = 4,
-                          bar_centroids=None, bar_bandwidths=None) -> Set[int]:
-    """Indices of bars that belong to runs of >= `min_consecutive_bars` bars with energy >= threshold.
-    (The spectral-fusion branch of the reference needs per-bar centroid/bandwidth, which the VPBD path never passes.)"""
-    e = np.asarray(list(bar_energies), dtype=np.float32)
-    if e.size == 0:
-        return set()
-    if bar_centroids or bar_bandwidths:
-        raise NotImplementedError("spectral-fusion chorus detection belongs to the hybrid_mdd mode (out of scope)")
-    high = e >= float(energy_threshold)
-    need = max(1, int(min_consecutive_bars))
-    bars: Set[int] = set()
-    run_start = None
-    for i, flag in enumerate(high):
-        if flag:
-            if run_start is None:
-                run_start = i
-        else:
-            if run_start is not None and i - run_start >= need:
-                bars.update(range(run_start, i))
-            run_start = None
-    if run_start is not None and len(high) - run_start >= need:
-        bars.update(range(run_start, len(high)))
-    return bars
 
 
 def _bar_times(beats: np.ndarray, duration_s: float, beats_per_bar: int = 4) -> List[float]:

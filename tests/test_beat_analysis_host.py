@@ -1,0 +1,254 @@
+"""Host side of the beat / bar analysis layer: both branches of `detect_chorus_regions` against the reference's recorded
+results (tests/golden/beat_analysis.npz), the bar boundary and frame-range construction against boolean masks, and the ABI of
+include/audiocut_hip_beat.h (exported, bound, versioned on its own, bad arguments refused).  CPU only."""
+import ast
+import json
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+from audio_cut_amd.analysis import beat_analyzer as BA
+from audio_cut_amd.analysis import chorus_regions as CR
+from audio_cut_amd.testing import beat_cases
+
+ROOT = Path(__file__).resolve().parent.parent
+
+# every export of include/audiocut_hip_beat.h -> the GPU test that calls it directly and compares it with a reference, or "host-only"
+BEAT_EXPORT_TESTS = {
+    "ac_beat_abi_version": "host-only",
+    "ac_stft2048_centroid_bandwidth": "test_beat_analysis_gpu::test_centroid_bandwidth_against_librosa",
+    "ac_bar_means3": "test_beat_analysis_gpu::test_bar_means3_against_numpy",
+}
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    return np.load(golden_dir / "beat_analysis.npz")
+
+
+def _cases(golden):
+    return json.loads(str(golden["cases"]))
+
+
+# ---- detect_chorus_regions against the fixture ---------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [c["name"] for c in beat_cases.CASES])
+def test_chorus_regions_match_the_reference(golden, name):
+    e, c, b = (golden[f"{name}__{k}"] for k in ("bar_energies", "bar_centroids", "bar_bandwidths"))
+    tempo, bar_duration, thr, cv, fused_thr = (float(v) for v in golden[f"{name}__scalars"])
+    fused = CR.detect_chorus_regions(list(e), thr, bar_centroids=list(c), bar_bandwidths=list(b))
+    assert sorted(fused) == [int(i) for i in golden[f"{name}__chorus_bars"]]
+    plain = CR.detect_chorus_regions(list(e), thr)
+    assert sorted(plain) == [int(i) for i in golden[f"{name}__chorus_bars_energy"]]
+    # the quantities the decision is taken on: float32 arithmetic, so a few float32 ulps of the values (all within [0, 1])
+    score, got_thr, got_cv = CR.fused_scores(e, c, b)
+    assert score.dtype == np.float32 and np.max(np.abs(score.astype(np.float64) - golden[f"{name}__fused_scores"])) <= 1e-6
+    assert abs(got_thr - fused_thr) <= 1e-6 and abs(got_cv - cv) <= 1e-6 * max(1.0, cv)
+    # arrays are taken like lists
+    assert CR.detect_chorus_regions(e, thr, bar_centroids=c, bar_bandwidths=b) == fused
+
+
+def test_fixture_covers_what_it_must(golden):
+    cases = _cases(golden)
+    assert [c["name"] for c in cases] == [c["name"] for c in beat_cases.CASES]
+    for stored, live in zip(cases, beat_cases.CASES):
+        assert {k: stored[k] for k in live} == live                              # the fixture was generated from these very cases
+    cvs = {c["name"]: float(golden[f"{c['name']}__scalars"][3]) for c in cases}
+    assert any(v < 0.15 for v in cvs.values()) and any(v > 0.4 for v in cvs.values()) and any(0.15 <= v <= 0.4 for v in cvs.values())
+    runs = lambda bars: sum(1 for b in bars if b - 1 not in set(bars))
+    assert any(runs([int(i) for i in golden[f"{c['name']}__chorus_bars"]]) > 1 for c in cases)
+    assert any(len(golden[f"{c['name']}__beats"]) < c["time_signature"] for c in cases)
+    assert any(len(golden[f"{c['name']}__beats"]) % c["time_signature"] for c in cases if len(golden[f"{c['name']}__beats"]) >= 4)
+    assert any(c["stereo"] for c in cases)
+    for key in ("bar_rel", "score_abs", "cv_abs", "range_abs"):
+        assert float(golden[f"min_margin_{key}"]) >= 1e-3
+
+
+# ---- the branches, case by case ---------------------------------------------------------------------------------------------
+def _lists(n=12, seed=0):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(0.1, 1.0, n), rng.uniform(500.0, 4000.0, n), rng.uniform(800.0, 3000.0, n)
+
+
+def _fusion_by_hand(e, c, b, weights, min_run=4):
+    def norm(v):
+        a = np.asarray(v, dtype=np.float32)
+        lo, hi = float(a.min()), float(a.max())
+        return (a - lo) / (hi - lo) if hi - lo > 1e-6 else np.zeros_like(a)
+    score = norm(e) * weights[0] + norm(c) * weights[1] + norm(b) * weights[2]
+    flags = score >= float(np.percentile(score, 60))
+    out, i = set(), 0
+    while i < len(flags):
+        j = i
+        while j < len(flags) and flags[j]:
+            j += 1
+        if j - i >= min_run:
+            out.update(range(i, j))
+        i = max(j, i + 1)
+    return out
+
+
+@pytest.mark.parametrize("spread,weights", [(0.02, (0.3, 0.4, 0.3)), (0.45, (0.5, 0.25, 0.25)), (3.0, (0.6, 0.2, 0.2))])
+def test_weight_regimes(spread, weights):
+    _, c, b = _lists(40, seed=3)
+    rng = np.random.default_rng(4)
+    e = 1.0 + spread * rng.uniform(-1.0, 1.0, 40)
+    e = np.abs(e) + 0.05
+    e[10:18] += spread; e[25:31] += spread                            # the loud bars are the bright ones
+    cv = CR.energy_cv(np.asarray(e, dtype=np.float32))
+    assert CR.fusion_weights(cv) == weights, cv
+    # two blocks of bright, wide bars, so that there are runs to find
+    c[10:18] += 5000.0; b[10:18] += 4000.0; c[25:31] += 5000.0; b[25:31] += 4000.0
+    got = CR.detect_chorus_regions(list(e), 0.0, bar_centroids=list(c), bar_bandwidths=list(b))
+    assert got == _fusion_by_hand(e, c, b, weights) and got
+    assert CR.fusion_weights(0.15) == CR.fusion_weights(0.4) == (0.5, 0.25, 0.25)          # both bounds belong to the middle
+
+
+def test_zero_range_centroids_contribute_nothing():
+    e, _, b = _lists(20, seed=5)
+    flat = [1234.5] * 20
+    almost = [1234.5 + 1e-7 * i for i in range(20)]                   # a range under 1e-6 counts as none
+    for c in (flat, almost):
+        score, _, cv = CR.fused_scores(e, c, b)
+        w = CR.fusion_weights(cv)
+        ne = (np.float32(1) * (np.asarray(e, np.float32) - np.float32(e).min())) / (np.float32(e).max() - np.float32(e).min())
+        nb = (np.asarray(b, np.float32) - np.float32(b).min()) / (np.float32(b).max() - np.float32(b).min())
+        assert np.allclose(score, ne * w[0] + nb * w[2], rtol=0, atol=1e-6)
+    assert CR.detect_chorus_regions(e, 0.0, bar_centroids=flat, bar_bandwidths=b) == _fusion_by_hand(e, flat, b, CR.fusion_weights(cv))
+
+
+def test_unequal_or_missing_lists_fall_back_to_the_energy_branch():
+    e = [0.1, 0.9, 0.9, 0.9, 0.9, 0.1, 0.9, 0.9]
+    plain = CR.detect_chorus_regions(e, 0.5)
+    assert plain == {1, 2, 3, 4}
+    c, b = [5000.0] * 7, [100.0 * i for i in range(8)]
+    assert CR.detect_chorus_regions(e, 0.5, bar_centroids=c, bar_bandwidths=b) == plain       # centroids one short
+    assert CR.detect_chorus_regions(e, 0.5, bar_centroids=[], bar_bandwidths=b) == plain
+    assert CR.detect_chorus_regions(e, 0.5, bar_centroids=b, bar_bandwidths=None) == plain
+    assert CR.detect_chorus_regions(e, 0.5, bar_centroids=None, bar_bandwidths=None) == plain
+    # energy equal to the threshold counts as high
+    assert CR.detect_chorus_regions([0.5, 0.5, 0.5, 0.5], 0.5) == {0, 1, 2, 3}
+
+
+def test_empty_input_and_run_lengths():
+    assert CR.detect_chorus_regions([], 0.5) == set()
+    assert CR.detect_chorus_regions([], 0.5, bar_centroids=[], bar_bandwidths=[]) == set()
+    e = [0.9, 0.1, 0.9, 0.9, 0.1, 0.9, 0.9, 0.9]
+    for need in (0, 1):                                                     # 0 is taken as 1: every high bar is a run
+        assert CR.detect_chorus_regions(e, 0.5, min_consecutive_bars=need) == {0, 2, 3, 5, 6, 7}
+    assert CR.detect_chorus_regions(e, 0.5, min_consecutive_bars=2) == {2, 3, 5, 6, 7}
+    assert CR.detect_chorus_regions(e, 0.5, min_consecutive_bars=3) == {5, 6, 7}               # a run ending at the last bar
+    assert CR.detect_chorus_regions(e, 0.5, min_consecutive_bars=4) == set()
+
+
+def test_beat_candidates_reexports_and_takes_spectral_lists():
+    from audio_cut_amd.cutting import beat_candidates as BC
+    assert BC.detect_chorus_regions is CR.detect_chorus_regions
+    e, c, b = _lists(30, seed=9)
+    c[5:12] += 6000.0; b[5:12] += 5000.0
+    got = BC.detect_chorus_regions(list(e), 0.0, bar_centroids=list(c), bar_bandwidths=list(b))       # raised NotImplementedError before
+    assert got == CR.detect_chorus_regions(list(e), 0.0, bar_centroids=list(c), bar_bandwidths=list(b)) and got
+
+
+# ---- bar boundaries and frame ranges ---------------------------------------------------------------------------------------
+def test_generate_bar_boundaries():
+    beats = np.array([0.4, 0.9, 1.4, 1.9, 2.4, 2.9, 3.4, 3.9, 4.4, 4.9])
+    assert np.array_equal(BA._generate_bar_boundaries(beats, 6.0, 4), np.array([0.4, 2.4, 4.4, 6.0]))
+    assert np.array_equal(BA._generate_bar_boundaries(beats[:8], 6.0, 4), np.array([0.4, 2.4, 6.0]))
+    assert np.array_equal(BA._generate_bar_boundaries(beats, 6.0, 3), np.array([0.4, 1.9, 3.4, 4.9, 6.0]))
+    # fewer beats than a bar: a grid from 0 at the beats' mean spacing, or at 120 BPM
+    few = np.array([0.5, 1.1, 1.7])
+    step = float(np.mean(np.diff(few))) * 4
+    assert np.array_equal(BA._generate_bar_boundaries(few, 20.0, 4), np.arange(0, 20.0 + step, step))
+    for none in (np.array([]), np.array([3.0])):
+        assert np.array_equal(BA._generate_bar_boundaries(none, 5.0, 4), np.arange(0, 7.0, 2.0))
+
+
+def _ranges_from_masks(times, bar_times):
+    out = []
+    for a, b in zip(bar_times[:-1], bar_times[1:]):
+        out.append(np.flatnonzero((times >= a) & (times < b)))
+    return out
+
+
+@pytest.mark.parametrize("sr,hop", [(44100, 512), (44100, 441), (22050, 512)])
+def test_frame_ranges_agree_with_boolean_masks(sr, hop):
+    rng = np.random.default_rng(sr + hop)
+    n_frames = 1 + (30 * sr) // hop
+    times = BA.frame_times(n_frames, sr, hop)
+    assert np.array_equal(times, (np.arange(n_frames) * hop).astype(int) / float(sr)) and np.all(np.diff(times) > 0)
+    exact = times[rng.integers(0, n_frames, size=6)]                              # boundaries that ARE frame times
+    lists = [np.sort(np.concatenate((rng.uniform(0.0, 30.0, 40), exact))),        # increasing, past either end too
+             np.concatenate(([0.0], np.sort(rng.uniform(-1.0, 33.0, 25)), [31.0])),
+             rng.uniform(0.0, 30.0, 30),                                          # not monotone: some bars end before they start
+             np.array([5.0, 5.0, 4.0, 10.0, 10.0, 2.0, 40.0]),
+             np.arange(0, 30.0 + 2.4, 2.4)]
+    for bar_times in lists:
+        lo, hi = BA.bar_frame_ranges(times, bar_times)
+        assert lo.dtype == hi.dtype == np.int64 and len(lo) == len(bar_times) - 1
+        assert np.all(lo >= 0) and np.all(hi <= n_frames)
+        for a, b, idx in zip(lo, hi, _ranges_from_masks(times, bar_times)):
+            assert np.array_equal(np.arange(a, max(a, b)), idx)
+
+
+def test_result_counts_and_mono():
+    r = BA.BeatAnalysisResult(tempo=120.0, beat_times=np.arange(7) * 0.5, bar_times=np.array([0.0, 2.0, 4.0]), bar_duration=2.0,
+                              bar_energies=[0.1, 0.2])
+    assert (r.num_beats, r.num_bars) == (7, 2) and r.high_energy_bars == set() and r.bar_spectral_centroids == []
+    assert BA.BeatAnalysisResult(120.0, None, np.array([0.0]), 2.0, []).num_bars == 0
+    st = np.random.default_rng(1).standard_normal((2, 100)).astype(np.float32)
+    assert np.array_equal(BA._ensure_mono(st), (st[0] + st[1]) * np.float32(0.5))
+    assert BA.BeatAnalyzer(48000, hop_length=256).last_result is None
+
+
+# ---- ABI ------------------------------------------------------------------------------------------------------------------------
+def _names(header: str) -> set:
+    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from audio_cut_amd import _native
+    if not _native.library_path().exists():
+        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
+    return _native.load()
+
+
+def test_beat_header_symbols_exported_and_bound(lib):
+    from audio_cut_amd import _native
+    names = _names("audiocut_hip_beat.h")
+    assert names == set(_native.BEAT_SIGNATURES)
+    for name in names:
+        assert hasattr(lib, name), f"{name} declared in the beat header but not exported"
+    assert lib.ac_beat_abi_version() == 1
+    # argument counts of the prototypes against the ctypes tables
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_beat.h").read_text(), flags=re.S)
+    for name, args in re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        n_args = 0 if args.strip() == "void" else len(args.split(","))
+        assert n_args == len(_native.BEAT_SIGNATURES[name][1]), name
+    # the other headers' surfaces are untouched
+    main = _names("audiocut_hip.h")
+    assert main == set(_native.SIGNATURES) and not (main & names) and len(main) == 49
+    assert lib.ac_abi_version() == 6 and lib.ac_stereo_abi_version() == 1 and lib.ac_onset_abi_version() == 1
+    assert not (names & (_names("audiocut_hip_stereo.h") | _names("audiocut_hip_onset.h")))
+
+
+def test_every_beat_export_names_its_direct_test():
+    assert set(BEAT_EXPORT_TESTS) == _names("audiocut_hip_beat.h")
+    for ref in set(BEAT_EXPORT_TESTS.values()) - {"host-only"}:
+        module, name = ref.split("::")
+        tree = ast.parse((ROOT / "tests" / f"{module}.py").read_text())
+        assert name in {node.name for node in tree.body if isinstance(node, ast.FunctionDef)}, f"{ref} does not exist"
+
+
+def test_beat_entry_points_reject_bad_arguments(lib):
+    # null context / sizes out of range come back as AC_E_INVALID, never as a launch
+    assert lib.ac_stft2048_centroid_bandwidth(None, None, 0, 0, 44100.0, None, None, 0, None) == -1
+    assert lib.ac_bar_means3(None, None, 0, None, None, 0, None, None, 0, None, None) == -1
+
+
+def test_nothing_in_the_package_imports_the_oracle():
+    for path in (ROOT / "audio_cut_amd").rglob("*.py"):
+        assert not re.search(r"^\s*(from|import)\s+oracle\b", path.read_text(), flags=re.M), path
