@@ -213,13 +213,16 @@ __global__ __launch_bounds__(256) void k_silero_frontend(const float* __restrict
     __syncthreads();
     // ---- input half of the LSTM gates: gates_x[w][g] = bias_ih[g] + bias_hh[g] + sum_j weight_ih[g][j] feat[j]
     for (int g = tid; g < 4 * SV_H; g += 256) {
+        // the bias goes in last: the forget gate's is of order 1 while the 128 products are small, and a sum that starts at the
+        // bias rounds every one of them at the bias's ulp (measured: 8 float32 noise levels on quiet input, 1 with the bias last)
         float acc[SV_NW];
 #pragma unroll
-        for (int i = 0; i < SV_NW; ++i) acc[i] = W.bsum[g];
+        for (int i = 0; i < SV_NW; ++i) acc[i] = 0.f;
         for (int j = 0; j < SV_H; ++j) sv_fma8(acc, W.wih_t[j * 4 * SV_H + g], &s_a4[j * SV_NW]);
+        const float bias = W.bsum[g];
 #pragma unroll
         for (int i = 0; i < SV_NW; ++i)
-            if (w0 + i < n_win) gates_x[(size_t)(w0 + i) * 4 * SV_H + g] = acc[i];
+            if (w0 + i < n_win) gates_x[(size_t)(w0 + i) * 4 * SV_H + g] = acc[i] + bias;
     }
 }
 

@@ -352,7 +352,8 @@ int ac_resample_poly_segments(ac_ctx* ctx, const float* x, const int64_t* in_off
  * win_start = -(index) - 1: its context is zeros), reflect-padded by 64, STFT as a stride-128 convolution with
  * forward_basis_buffer (basis_t [256][258], transposed), magnitude, Conv1d(129,128,3) / (128,64,3,s2) / (64,64,3,s2) /
  * (64,128,3) each + ReLU (weights as [c_in * 3 + tap][c_out]), then gates_x[w][512] = weight_ih feat + bias_ih + bias_hh
- * (wih_t [128][512], bias_sum [512]).  x16 must be readable 64 samples before every non-first window and 576 after its start. */
+ * (wih_t [128][512], bias_sum [512]).  x16 must be readable from 64 samples before the start of every non-first
+ * window (from the start itself for a first window) to 512 samples after it. */
 int ac_silero_frontend(ac_ctx* ctx, const float* x16, const int64_t* win_start, int n_windows, const float* basis_t,
                        const float* c1, const float* b1, const float* c2, const float* b2, const float* c3, const float* b3,
                        const float* c4, const float* b4, const float* wih_t, const float* bias_sum, float* gates_x, void* stream);

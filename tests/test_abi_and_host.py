@@ -402,9 +402,9 @@ EXPORT_TESTS = {
     "ac_resample_poly": "test_export_loader::test_resample_poly_kernel_vs_oracle",
     "ac_resample_poly_segments": "test_kernels_edges_gpu::test_resample_poly_segments_edges",
     "ac_pack_pcm24": "test_export_loader::test_pack_pcm24_kernel_vs_host",
-    "ac_silero_frontend": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
-    "ac_silero_lstm": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
-    "ac_silero_out": "test_silero_vad::test_silero_network_and_timestamps_against_oracle",
+    "ac_silero_frontend": "test_silero_kernels_gpu::test_frontend_against_float64",
+    "ac_silero_lstm": "test_silero_kernels_gpu::test_lstm_synthetic_gates",
+    "ac_silero_out": "test_silero_kernels_gpu::test_out_against_float64",
 }
 
 
