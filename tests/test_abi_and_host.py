@@ -376,9 +376,9 @@ EXPORT_TESTS = {
     "ac_zero_cross_nearest": "test_cut_refine_edges_gpu::test_zero_cross_nearest_edges",
     "ac_quiet_guard_slow": "test_cut_refine_edges_gpu::test_quiet_guard_slow_edges",
     "ac_pause_cut_points": "test_cut_refine_edges_gpu::test_pause_cut_points_edges",
-    "ac_mdx_stft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
-    "ac_mdx_istft": "test_kernels_gpu::test_mdx_stft_istft_assemble",
-    "ac_mdx_assemble_ola": "test_kernels_gpu::test_mdx_stft_istft_assemble",
+    "ac_mdx_stft": "test_mdx_kernels_gpu::test_stft_against_float64",
+    "ac_mdx_istft": "test_mdx_kernels_gpu::test_istft_against_float64",
+    "ac_mdx_assemble_ola": "test_mdx_kernels_gpu::test_assemble_ola_exact_over_plans",
     "ac_mdx_chunk_vocal": "test_kernels_edges_gpu::test_mdx_chunk_vocal_edges",
     "ac_sum_squares": "test_kernels_edges_gpu::test_mean_square_partials_edges",
     "ac_window_sum_squares": "test_kernels_gpu::test_window_mean_squares_is_the_per_window_mean_square_bit_for_bit",

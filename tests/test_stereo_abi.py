@@ -17,8 +17,8 @@ SR = 44100
 # every export of include/audiocut_hip_stereo.h -> the GPU test that calls it directly and compares it with a reference, or "host-only"
 STEREO_EXPORT_TESTS = {
     "ac_stereo_abi_version": "host-only",
-    "ac_mdx_stft_stereo": "test_stereo_kernels_gpu::test_mdx_stft_stereo_against_oracle",
-    "ac_mdx_assemble_ola_stereo": "test_stereo_kernels_gpu::test_mdx_assemble_ola_stereo_exact",
+    "ac_mdx_stft_stereo": "test_mdx_kernels_gpu::test_stft_against_float64",
+    "ac_mdx_assemble_ola_stereo": "test_mdx_kernels_gpu::test_assemble_ola_exact_over_plans",
     "ac_mdx_chunk_vocal_stereo": "test_stereo_kernels_gpu::test_mdx_chunk_vocal_stereo_exact",
 }
 

@@ -7,6 +7,7 @@ import torch
 
 from audio_cut_amd._native import NativeError
 from audio_cut_amd.testing import signals
+from mdx_refs import restated_stereo_ola as _restated_stereo_ola
 from oracle import chunking as OC, separator as OS
 
 pytestmark = pytest.mark.gpu
@@ -66,22 +67,6 @@ def test_mdx_stft_stereo_against_oracle(hip_ctx, stereo):
     for bad in (xd.t().contiguous(), xd[:, ::2], torch.stack([xd[0]] * 3)):
         with pytest.raises(NativeError):
             hip_ctx.mdx_stft(bad, d_cs, d_cl, d_wi)
-
-
-def _restated_stereo_ola(x, wave, ranges, base, nbs):
-    """Per channel: the effective-region overlap-add of w_c and m_c - w_c, summed in chunk order, divided by the count."""
-    n = x.shape[1]
-    v = np.zeros((2, n), np.float32); r = np.zeros((2, n), np.float32); cnt = np.zeros(n, np.float32)
-    for c, (cs, ce, es, ee) in enumerate(ranges):
-        if ee <= es:
-            continue
-        w = wave[base[c]:base[c] + nbs[c]][:, :, OC.TRIM:-OC.TRIM]
-        w = w.transpose(1, 0, 2).reshape(2, -1)[:, es - cs: ee - cs]
-        v[:, es:ee] += w
-        r[:, es:ee] += x[:, es:ee] - w
-        cnt[es:ee] += 1.0
-    cnt[cnt == 0.0] = 1.0
-    return v / cnt, r / cnt
 
 
 def test_mdx_assemble_ola_stereo_exact(hip_ctx, stereo):
