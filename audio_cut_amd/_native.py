@@ -159,6 +159,36 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _packed(name: str, t: Optional[torch.Tensor], n_bytes: Optional[int]) -> None:
+    """Host-side guard of a pre-packed weight buffer (the kernels read it by the layouts of separation/conv_pack.py and would run past
+    the end of a smaller one): its size must be EXACTLY what the call's shape implies - a larger buffer would be safe to read, but it
+    was packed for another shape or in another kernel's layout, so equality is intended (pass a view of the right length, not an
+    arena).  `n_bytes` None = a shape the kernel does not tile: the library refuses it itself (a null pointer likewise)."""
+    if t is None or n_bytes is None:
+        return
+    have = t.numel() * t.element_size()
+    if have != n_bytes:
+        raise NativeError(f"{name}: the packed weights hold {have} bytes, the shape implies {n_bytes} (see separation/conv_pack.py)")
+
+
+def _conv3x3_packed_bytes(c_in: int, c_out: int, cob: int, stage: int) -> Optional[int]:
+    """pack_conv3x3 (stage 16: five k-steps per 16 channels) / pack_conv3x3_w96 (stage 8: three k-steps per 8 channels), `cob`
+    output channels per block: [C_out / cob][C_in / stage][k-steps][hi, lo][cob / 16][64][8] float16.
+    None outside the channel condition of cv_launch (csrc/ac_conv.hip) / w9_launch (csrc/ac_conv96.hip): keep in step with their AC_REQUIRE."""
+    if c_in <= 0 or c_out <= 0 or c_in % 16 or c_out % cob:
+        return None
+    return (c_out // cob) * (c_in // stage) * (5 if stage == 16 else 3) * 2 * (cob // 16) * 64 * 8 * 2
+
+
+def _linear_packed_bytes(n: int, k: int, bn: int) -> Optional[int]:
+    """pack_linear: hi and lo float16 of [N'][K'], N' / K' = N / K rounded up to `bn` columns / 32 (bn 0: exact tiling, the TDF kernel:
+    None outside K % 32 == 0, N % 96 == 0 - keep in step with the AC_REQUIRE of ac_tdf_linear_f16x3, csrc/ac_gemm.hip)."""
+    if n <= 0 or k <= 0 or (bn == 0 and (n % 96 or k % 32)):
+        return None
+    n2 = -(-n // bn) * bn if bn else n
+    return 2 * n2 * (-(-k // 32) * 32) * 2
+
+
 class Context:
     """Per-device handle (ac_ctx) + thin typed wrappers; tensors must live on this device."""
 
@@ -840,12 +870,15 @@ class Context:
         if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
             raise NativeError(f"{name} expects a contiguous float32 NCHW tensor")
         b, c_in, h, w = x.shape
+        _packed(name, w_packed, _conv3x3_packed_bytes(c_in, int(c_out), *self._CONV3X3_LAYOUT[name]))
         if out is None:
             out = torch.empty((b, c_out, h, w), dtype=torch.float32, device=self.device)
         pi, po = self._amax_args(b, in_amax, out_amax, h, h)
         _check(fn(self._h, _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), b, c_in, c_out, h, w, float(w_unscale), int(relu), pi, po,
                   _stream()))
         return out
+
+    _CONV3X3_LAYOUT = {"conv3x3_f16x3": (48, 16), "conv3x3_f16x3_w96": (96, 8), "conv3x3_f16x3_s8": (48, 8)}     # (cob, stage)
 
     def conv3x3_f16x3(self, x: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, c_out: int, w_unscale: float = 1.0,
                       relu: bool = True, out: Optional[torch.Tensor] = None, in_amax: Optional[torch.Tensor] = None,
@@ -878,6 +911,7 @@ class Context:
         w1 = w1.reshape(w1.shape[0], -1)
         if w1.shape[1] != c0 or not w1.is_contiguous():
             raise NativeError("conv3x3_f16x3_first: w1 must be [C_in, C0(,1,1)] contiguous")
+        _packed("conv3x3_f16x3_first", w_packed, _conv3x3_packed_bytes(w1.shape[0], int(c_out), 48, 8))
         out = torch.empty((b, c_out, h, w), dtype=torch.float32, device=self.device)
         pi, po = self._amax_args(b, spec_amax, out_amax, h, h)
         _check(self.lib.ac_conv3x3_f16x3_first(self._h, _ptr(spec), _ptr(w1), _ptr(b1), _ptr(w_packed), _ptr(bias), _ptr(out), b, c0,
@@ -893,6 +927,8 @@ class Context:
         if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
             raise NativeError("tdf_linear_f16x3 expects a contiguous float32 NCHW tensor")
         b, c, t, k = x.shape
+        if c % 16 == 0 and t % 8 == 0:        # the row condition of ac_tdf_linear_f16x3's AC_REQUIRE (csrc/ac_gemm.hip; keep in step): else the library refuses the shape itself
+            _packed("tdf_linear_f16x3", w_packed, _linear_packed_bytes(int(n_out), k, 0))
         out = torch.empty((b, c, t, n_out), dtype=torch.float32, device=self.device)
         if resid is not None and (resid.shape != out.shape or not resid.is_contiguous() or resid.dtype != torch.float32):
             raise NativeError("tdf_linear_f16x3: residual must match the output")
@@ -909,6 +945,11 @@ class Context:
         if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
             raise NativeError("tdf_small_fused expects a contiguous float32 NCHW tensor")
         b, c, t, f = x.shape
+        hd = int(hidden)
+        # the F / Hd / M conditions of ac_tdf_small_fused's AC_REQUIRE (csrc/ac_tdf_small.hip; keep in step): else the library refuses the shape itself
+        if f > 0 and f % 32 == 0 and 0 < hd <= 48 and (b * c * t) % 32 == 0:      # pack_tdf_small: float32 [ceil(Hd / 16)][F / 16][64][4] and [F / 16][ceil(Hd / 4)][64]
+            _packed("tdf_small_fused (w1)", w1_packed, -(-hd // 16) * (f // 16) * 64 * 4 * 4)
+            _packed("tdf_small_fused (w2)", w2_packed, (f // 16) * -(-hd // 4) * 64 * 4)
         out = torch.empty_like(x)
         _, po = self._amax_args(b, None, out_amax, t, t)
         _check(self.lib.ac_tdf_small_fused(self._h, _ptr(x), _ptr(w1_packed), _ptr(w2_packed), _ptr(scale1), _ptr(shift1), _ptr(scale2),
@@ -923,6 +964,7 @@ class Context:
         w2 = weight.reshape(weight.shape[0], -1)
         if w2.shape[1] != c or not w2.is_contiguous():
             raise NativeError("conv1x1_small: weight must be [C_out, C_in(,1,1)] contiguous")
+        _packed("conv1x1_small (bias)", bias, w2.shape[0] * 4)                          # the weight's shape is checked above: only the bias is left
         out = torch.empty((b, w2.shape[0], h, w), dtype=torch.float32, device=self.device)
         _check(self.lib.ac_conv1x1_small(self._h, _ptr(x), _ptr(w2), _ptr(bias), _ptr(out), b, c, w2.shape[0], h * w, int(relu), _stream()))
         return out
@@ -933,6 +975,7 @@ class Context:
         if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
             raise NativeError("down2x_f16x3 expects a contiguous float32 NCHW tensor")
         b, c, h, w = x.shape
+        _packed("down2x_f16x3", w_packed, _linear_packed_bytes(int(c_out), 4 * c, 96))
         out = torch.empty((b, c_out, h // 2, w // 2), dtype=torch.float32, device=self.device)
         pi, po = self._amax_args(b, in_amax, out_amax, h, h // 2)
         _check(self.lib.ac_down2x_f16x3(self._h, _ptr(x), _ptr(w_packed), _ptr(bias), _ptr(out), b, c, c_out, h, w, float(w_unscale),
@@ -946,6 +989,7 @@ class Context:
         if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
             raise NativeError("up2x_f16x3 expects a contiguous float32 NCHW tensor")
         b, c, h, w = x.shape
+        _packed("up2x_f16x3", w_packed, _linear_packed_bytes(4 * int(c_out), c, 96))
         out = torch.empty((b, c_out, 2 * h, 2 * w), dtype=torch.float32, device=self.device)
         if skip is not None and (skip.shape != out.shape or not skip.is_contiguous() or skip.dtype != torch.float32):
             raise NativeError("up2x_f16x3: skip must match the output")

@@ -183,7 +183,8 @@ int ac_window_sum_squares(ac_ctx* ctx, const float* x, int64_t n, const int64_t*
  * separation/backends.py:358.  w_packed = weights (BatchNorm folded, scaled by a power of two 1/w_unscale)
  * pre-arranged in MFMA fragment order by audio_cut_amd.separation.conv_pack.pack_conv3x3
  * ([C_out/48][C_in/16][5][hi,lo][3][64] fragments of 8 f16).  C_in % 16 == 0, C_out % 48 == 0, H % 8 == 0,
- * W % 32 == 0.  out = conv(x) * w_unscale + bias[c], followed by ReLU when relu != 0.
+ * W % 32 == 0, H * W < 2^31, fewer than 2^31 workgroups (B * C_out / 48 * H / 8 * W / 32); C_in and C_out need not be equal.
+ * out = conv(x) * w_unscale + bias[c], followed by ReLU when relu != 0.
  *
  * "amax" (every split-float16 kernel below takes the pair): in_amax [B][H] float32 = max |x| of each batch item and row of the
  * time axis H (H = T for the TDF kernels) of the INPUT tensor, as written by the kernel that produced it.  A kernel takes the
@@ -202,7 +203,8 @@ int ac_conv3x3_f16x3(ac_ctx* ctx, const float* x, const void* w_packed, const fl
 
 /* The graph's first (4 -> g) and last (g -> 4) 1x1 convolutions (Conv nodes at the two ends of the graph run at
  * separation/backends.py:358; oracle/separator.py:78,94): float32 FMAs at streaming rate.
- * out[b][co][p] = act(bias[co] + sum_ci w[co][ci] x[b][ci][p]); x [B][C_in][P], P % 4 == 0, min(C_in, C_out) <= 8. */
+ * out[b][co][p] = act(bias[co] + sum_ci w[co][ci] x[b][ci][p]); x [B][C_in][P], P % 4 == 0, min(C_in, C_out) <= 8, B <= 65535
+ * (the batch is the grid's second dimension). */
 int ac_conv1x1_small(ac_ctx* ctx, const float* x, const float* w, const float* bias, float* out, int B, int C_in, int C_out,
                      long long P, int relu, void* stream);
 
@@ -213,7 +215,7 @@ int ac_conv1x1_small(ac_ctx* ctx, const float* x, const float* w, const float* b
  * x [M][K] float32 (the NCHW activation as rows (b, c, t)), y / resid [M][N]; w_packed from
  * audio_cut_amd.separation.conv_pack.pack_linear ([N/BN][K/32][hi,lo][BN/16][64] fragments of 8 f16, BN = 192 when
  * N % 192 == 0 else 96).  M = items * C * T with C % 16 == 0, T % 8 == 0 (a workgroup tile is 16 channels x 8 time rows x 192 or
- * 96 columns), K % 32 == 0, N % 96 == 0. */
+ * 96 columns), K % 32 == 0, N % 96 == 0, fewer than 2^31 - 8 workgroups (M / 128 * N / (192 or 96)). */
 int ac_tdf_linear_f16x3(ac_ctx* ctx, const float* x, const void* w_packed, const float* scale, const float* shift,
                         const float* resid, float* y, long long M, int N, int K, int T, int C, float w_unscale,
                         const float* in_amax, float* out_amax /* [M / (C*T)][T] */, void* stream);
@@ -221,8 +223,9 @@ int ac_tdf_linear_f16x3(ac_ctx* ctx, const float* x, const void* w_packed, const
 /* Both TDF layers + residual of a block at the deep levels (F = 384 / 192 / 96, bottleneck Hd = F / 8 <= 48: too narrow for
  * ac_tdf_linear_f16x3), one kernel, exact float32 on v_mfma_f32_16x16x4_f32 (same graph nodes as ac_tdf_linear_f16x3):
  *   y[m][n] = x[m][n] + relu(scale2[c] * sum_j relu(scale1[c] * sum_f x[m][f] w1[j][f] + shift1[c]) w2[n][j] + shift2[c])
- * w1_packed / w2_packed from conv_pack.pack_tdf_small.  M % 32 == 0, F % 32 == 0, x != y.  out_amax [M / (C*T)][T] as above
- * (needs (C * T) % 32 == 0); no in_amax: nothing is split. */
+ * w1_packed / w2_packed from conv_pack.pack_tdf_small.  M % 32 == 0, F % 32 == 0, 1 <= Hd <= 48 (any width in that range: the
+ * packed weights are zero padded to 16 / 4), T > 0, C > 0, x != y.  C * T need not be a multiple of 32 (the channel is taken per
+ * row) unless out_amax [M / (C*T)][T] (as above) is requested: that needs (C * T) % 32 == 0; no in_amax: nothing is split. */
 int ac_tdf_small_fused(ac_ctx* ctx, const float* x, const void* w1_packed, const void* w2_packed, const float* scale1,
                        const float* shift1, const float* scale2, const float* shift2, float* y, long long M, int F, int Hd,
                        int T, int C, float* out_amax, void* stream);
@@ -234,7 +237,8 @@ int ac_tdf_small_fused(ac_ctx* ctx, const float* x, const void* w1_packed, const
  *   up:   out[b][co][2y+dy][2x+dx] = relu(bias[co] + w_unscale * sum x[b][ci][y][x] w[ci][co][dy][dx]) * skip[...]  (skip may be NULL)
  * x [B][C_in][H][W] float32 NCHW; w_packed = conv_pack.pack_linear(W, bn=96) of W[co][(ci,dy,dx)] (down) or
  * W[(co,dy,dx)][ci] (up), zero padded to N % 96 == 0, K % 32 == 0.  Pixels per image on the GEMM's M axis
- * ((H/2)*(W/2) down, H*W up) % 128 == 0; W % 4 == 0; down: H even, C_in % 8 == 0; up: 4*C_out % 96 == 0.
+ * ((H/2)*(W/2) down, H*W up) % 128 == 0; W % 4 == 0; down: H even, C_in % 8 == 0, any C_out (columns beyond it are masked);
+ * up: 4*C_out % 96 == 0, any C_in (channels beyond it are masked); 4 * H * W < 2^31; fewer than 2^31 - 8 workgroups.
  * With in_amax / out_amax: down needs (W/2) % 4 == 0, up needs W >= 64 and W % 4 == 0 (a staged quad of pixels is scaled with
  * the maximum of ONE input row, so it must not straddle two rows). */
 int ac_down2x_f16x3(ac_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* out, int B, int C_in, int C_out,
@@ -313,7 +317,8 @@ int ac_resample_poly(ac_ctx* ctx, const float* x, int64_t n, int up, int down, c
  * 0x7FFFFF / 0x800000 (pcm.c f2let_clip_array).  out [3 * n] bytes. */
 int ac_pack_pcm24(ac_ctx* ctx, const float* x, int64_t n, unsigned char* out, void* stream);
 
-/* ac_conv3x3_f16x3_s8 (w_packed in its 48-channel layout: conv_pack.pack_conv3x3_w96(w, 48); C_in <= 64) with the graph's first
+/* ac_conv3x3_f16x3_s8 (w_packed in its 48-channel layout: conv_pack.pack_conv3x3_w96(w, 48); C_in % 16 == 0, C_in <= 64,
+ * C_out % 48 == 0, H % 8 == 0, W % 32 == 0; amax_gain, amax_offs >= 0) with the graph's first
  * 1x1 convolution (spec [B][C0][H][W], C0 <= 4, w1 [C_in][C0], b1 [C_in], + ReLU; the first Conv + BatchNormalization + Relu
  * nodes at separation/backends.py:358) fused into its loader: a thread's spectrogram float4s are loaded once and the
  * C_in-channel tensor is generated per staged pixel with ac_conv1x1_small's arithmetic (bit-identical), never written to HBM.
@@ -331,7 +336,8 @@ int ac_conv3x3_f16x3_w96(ac_ctx* ctx, const float* x, const void* w_packed, cons
                          int C_out, int H, int W, float w_unscale, int relu, const float* in_amax, float* out_amax, void* stream);
 
 /* The 8-channel-stage kernel with 48 output channels per workgroup, three workgroups per CU (C_in % 16 == 0, C_out % 48 == 0;
- * conv_pack.pack_conv3x3_w96(w, cob=48)): the layers ac_conv3x3_f16x3_w96 cannot take. */
+ * conv_pack.pack_conv3x3_w96(w, cob=48)): the layers ac_conv3x3_f16x3_w96 cannot take.  Both: H % 8 == 0, W % 32 == 0,
+ * H * W < 2^31, fewer than 2^31 workgroups. */
 int ac_conv3x3_f16x3_s8(ac_ctx* ctx, const float* x, const void* w_packed, const float* bias, float* out, int B, int C_in,
                         int C_out, int H, int W, float w_unscale, int relu, const float* in_amax, float* out_amax, void* stream);
 

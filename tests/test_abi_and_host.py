@@ -57,6 +57,53 @@ def test_product_fails_loudly_without_gpu():
         PureVocalPauseDetector(SR).detect_pure_vocal_pauses(np.zeros(SR, np.float32))
 
 
+def test_unet_wrappers_check_the_packed_weight_size_on_the_host(lib):
+    """The nine U-Net wrappers hand `w_packed` to kernels that read it by the layouts of separation/conv_pack.py: a buffer that is not
+    the size the call's shape implies raises NativeError on the host, before anything is allocated or launched (CPU tensors, no
+    context handle: reaching the library would fail differently), and the expected sizes are those the pack functions produce."""
+    import torch
+    from audio_cut_amd import _native
+    from audio_cut_amd.separation import conv_pack as CP
+    nbytes = lambda a: a.size * a.itemsize
+    w = np.ones((96, 48, 3, 3), np.float32)
+    assert nbytes(CP.pack_conv3x3(w)[0]) == _native._conv3x3_packed_bytes(48, 96, 48, 16)
+    assert nbytes(CP.pack_conv3x3_w96(w, 96)[0]) == _native._conv3x3_packed_bytes(48, 96, 96, 8)
+    assert nbytes(CP.pack_conv3x3_w96(w, 48)[0]) == _native._conv3x3_packed_bytes(48, 96, 48, 8)
+    assert _native._conv3x3_packed_bytes(40, 96, 96, 8) is None and _native._conv3x3_packed_bytes(48, 48, 96, 8) is None
+    for n, k in ((96, 32), (192, 64), (288, 32), (1536, 32)):
+        assert nbytes(CP.pack_linear(np.ones((n, k), np.float32))[0]) == _native._linear_packed_bytes(n, k, 0)
+    for n, k in ((8, 32), (104, 32), (96, 1), (288, 33), (144, 240)):
+        assert nbytes(CP.pack_linear(np.ones((n, k), np.float32), bn=96)[0]) == _native._linear_packed_bytes(n, k, 96)
+    assert _native._linear_packed_bytes(48, 32, 0) is None and _native._linear_packed_bytes(96, 48, 0) is None
+
+    ctx = _native.Context.__new__(_native.Context)           # no device, no handle: only the host-side checks can run
+    ctx.device, ctx.lib, ctx._h = torch.device("cpu"), lib, None
+    z = lambda *shape: torch.zeros(*shape)
+    i16 = lambda n_bytes: torch.zeros(n_bytes // 2, dtype=torch.int16)
+    conv = lambda ci, co, cob, st: _native._conv3x3_packed_bytes(ci, co, cob, st)
+    p1, p2 = CP.pack_tdf_small(np.ones((12, 32), np.float32), np.ones((32, 12), np.float32))
+    p1, p2 = torch.from_numpy(p1), torch.from_numpy(p2)
+    calls = {
+        "conv3x3_f16x3": lambda d: ctx.conv3x3_f16x3(z(1, 16, 8, 32), i16(conv(16, 48, 48, 16) + d), z(48), 48),
+        "conv3x3_f16x3_w96": lambda d: ctx.conv3x3_f16x3_w96(z(1, 16, 8, 32), i16(conv(16, 96, 96, 8) + d), z(96), 96),
+        "conv3x3_f16x3_s8": lambda d: ctx.conv3x3_f16x3_s8(z(1, 16, 8, 32), i16(conv(16, 48, 48, 8) + d), z(48), 48),
+        "conv3x3_f16x3_first": lambda d: ctx.conv3x3_f16x3_first(z(1, 4, 8, 32), z(16, 4), z(16), i16(conv(16, 48, 48, 8) + d), z(48), 48, 1.0),
+        "tdf_linear_f16x3": lambda d: ctx.tdf_linear_f16x3(z(1, 16, 8, 32), i16(2 * 96 * 32 * 2 + d), 96, z(16), z(16), 1.0),
+        "tdf_small_fused (w1)": lambda d: ctx.tdf_small_fused(z(1, 4, 8, 32), p1[:, :, :63] if d < 0 else torch.cat([p1, p1]), p2, 12, z(4), z(4), z(4), z(4)),
+        "tdf_small_fused (w2)": lambda d: ctx.tdf_small_fused(z(1, 4, 8, 32), p1, p2[:, :, :63] if d < 0 else torch.cat([p2, p2]), 12, z(4), z(4), z(4), z(4)),
+        "conv1x1_small": lambda d: ctx.conv1x1_small(z(1, 4, 1, 4), z(8, 4), z(8 + d // 2), relu=True),
+        "down2x_f16x3": lambda d: ctx.down2x_f16x3(z(1, 8, 16, 32), i16(2 * 96 * 32 * 2 + d), z(8), 8, 1.0),
+        "up2x_f16x3": lambda d: ctx.up2x_f16x3(z(1, 6, 2, 64), i16(2 * 96 * 32 * 2 + d), z(24), 24, 1.0),
+    }
+    for name, call in calls.items():
+        for delta in (-2, 2):                                # one float16 short (read past the end), one too many (another layout)
+            with pytest.raises(_native.NativeError, match="bytes, the shape implies"):
+                call(delta)
+    # the layout of the other conv kernel is refused although it was packed for the same weights
+    with pytest.raises(_native.NativeError, match="conv3x3_f16x3_s8: the packed weights hold"):
+        ctx.conv3x3_f16x3_s8(z(1, 16, 8, 32), torch.from_numpy(CP.pack_conv3x3(np.ones((48, 16, 3, 3), np.float32))[0].view(np.int16)), z(48), 48)
+
+
 def test_shared_unet_stream_needs_the_gate():
     """One U-Net stream for every worker is only safe together with the lock that keeps two tracks' launches from interleaving."""
     from audio_cut_amd.core.enhanced_vocal_separator import EnhancedVocalSeparator
