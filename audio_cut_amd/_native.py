@@ -47,6 +47,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so onset ABI version mismatch")
     if lib.ac_beat_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so beat ABI version mismatch")
+    if lib.ac_hybrid_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so hybrid ABI version mismatch")
     _lib = lib
     return lib
 
@@ -133,9 +135,16 @@ BEAT_SIGNATURES = {
     "ac_bar_means3": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I, _P, _P]),
 }
 
+# include/audiocut_hip_hybrid.h: the `hybrid_mdd` mode's quiet gate, exported by the same library and versioned on its own
+HYBRID_SIGNATURES = {
+    "ac_hybrid_abi_version": (C.c_int, []),
+    "ac_quiet_gate_meansq": (C.c_int, [_P, _P, _I64, _I64, _P, _I, _P, _I64, _P, _P, _P]),
+}
+
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
+                              *HYBRID_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -607,6 +616,29 @@ class Context:
         _check(self.lib.ac_bar_means3(self._h, _ptr(rms), nf, _ptr(centroid), _ptr(bandwidth), nf, ranges.data_ptr(),
                                       ranges.data_ptr() + 8 * nb, nb, _ptr(out), _stream()))
         return out.cpu().numpy()
+
+    # -- hybrid_mdd quiet gate (include/audiocut_hip_hybrid.h) -----------------------------------------
+    def quiet_gate(self, x: torch.Tensor, half_win: int, centers) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(block_ms [ceil(n / half_win)], point_ms [k], point_count [k]) of the resident signal `x`: the float64 mean square of
+        every consecutive block of `half_win` samples and of the window [c - half_win, c + half_win) clipped to the signal around
+        every centre c (any int64: outside the signal the count is 0 and the mean 0.0).  One staged upload (the centres), one
+        launch, one download: the three results share one device buffer."""
+        self._chk_f32(x)
+        half_win = int(half_win)
+        if half_win < 1:
+            raise ValueError("quiet_gate: half_win must be at least 1")
+        c = np.ascontiguousarray(np.asarray(centers, dtype=np.int64).reshape(-1))
+        n, k = int(x.numel()), int(c.size)
+        nb = -(-n // half_win)
+        if nb + k == 0:
+            return np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.float64), np.zeros(0, dtype=np.int64)
+        c_dev = self.to_device(c) if k else None
+        out = torch.empty(nb + 2 * k, dtype=torch.float64, device=self.device)        # block_ms | point_ms | point_count (int64 bits)
+        base = out.data_ptr()
+        _check(self.lib.ac_quiet_gate_meansq(self._h, _ptr(x) if n else None, n, half_win, _ptr(c_dev), k, base if nb else None, nb,
+                                             base + 8 * nb if k else None, base + 8 * (nb + k) if k else None, _stream()))
+        host = out.cpu().numpy()
+        return host[:nb].copy(), host[nb:nb + k].copy(), host[nb + k:].view(np.int64).copy()
 
     def local_valley(self, x: torch.Tensor, centers: np.ndarray, radius: int, win: int):
         """(orig_db, min_db, min_idx) per boundary, host arrays (see ac_local_valley)."""

@@ -2,8 +2,10 @@
 (`src/audio_cut/api.py:31-45`): load -> (resample) -> separate -> detect -> finalize -> boundary policy -> export ->
 SegmentManifest.
 
-Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, and `librosa_onset`
-(bar-aligned smart segmentation: mix segments by default, vocal segments on request, no full stems).
+Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, `librosa_onset`
+(bar-aligned smart segmentation: mix segments by default, vocal segments on request, no full stems) and
+`hybrid_mdd` (phrase-pause cuts snapped to beats in chorus bars: mix and vocal segments named `..._lib_D.D` where a segment ends on
+a beat, and the full vocal).
 Loader: PCM WAV / .npy, channel mean like `librosa.load(mono=True)`; a file whose rate differs from `audio.sample_rate`
 is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
@@ -204,10 +206,14 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         return {"success": False, "error": res.get("error"), "input_file": str(in_path), "mode": mode,
                 "timings": res.get("timings", {}), "processing_time": time.time() - t_start}
     smart = mode == "librosa_onset"
+    hybrid = mode == "hybrid_mdd"
     single = bool(res.get("single_segment"))            # `_create_single_segment_result`: only the mix, no duration tag
     if smart:       # `:1291-1322`: the mix segments by default; of the other kinds only the vocal segments are written in this mode
         plan = [k for k in _normalize_export_plan(export_types) if k in ("mix_segments", "vocal_segments")] if export_types \
             else ["mix_segments"]
+    elif hybrid:    # `:1580-1629`: mix and vocal segments and the full vocal; this mode writes no instrumental
+        kinds = ("mix_segments", "vocal_segments", "full_vocal")
+        plan = [k for k in _normalize_export_plan(export_types) if k in kinds] if export_types else list(kinds)
     else:
         plan = _normalize_export_plan(export_types) if (export_types or not single) else ["mix_segments"]
     cuts = [int(c) for c in res.get("cuts_samples", res["sample_boundaries"])]
@@ -215,6 +221,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     flags = list(res.get("segment_vocal_flags", [True] * len(spans)))
     durations = [(hi - lo) / float(sr) for lo, hi in spans]
     dmap = None if single else {i: d for i, d in enumerate(durations)}
+    # `hybrid_mdd` names its segments `segment_NNN_{human|music}[_lib]_D.D` (`:1586-1616`)
+    naming = {"lib_flags": list(res.get("segment_lib_flags", [])), "lib_suffix": res.get("lib_suffix", "_lib"), "index_offset": 1,
+              "always_append_duration": True} if hybrid else {}
     exp = ExportResult()
     exporter = SegmentExporter(sr)
     state = res.get("device_state") or {}
@@ -223,13 +232,14 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     mix_dev = state.get("mix_stereo", audio_dev) if channels == 2 else state.get("mix", audio_dev)
     if "mix_segments" in plan:
         mix_pk = PackedTrack(audio, sr, hip=hip, dev=mix_dev)
-        exp.mix_segment_files = exporter.export_spans(mix_pk, spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap)
+        exp.mix_segment_files = exporter.export_spans(mix_pk, spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap,
+                                                      **naming)
         exp.saved_files += exp.mix_segment_files
     vocal = res.get("vocal_track" + st)
     voc_pk = PackedTrack(vocal, sr, hip=hip, dev=state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
     if "vocal_segments" in plan and voc_pk is not None:
         exp.vocal_segment_files = exporter.export_spans(voc_pk, spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
-                                                        file_suffix="_vocal", duration_map=dmap)
+                                                        file_suffix="_vocal", duration_map=dmap, **naming)
         exp.saved_files += exp.vocal_segment_files
     if "full_vocal" in plan and voc_pk is not None:
         exp.full_vocal_file = exporter.export_full_track(voc_pk, out_dir / f"{in_path.stem}_{mode}_vocal_full_{np.shape(vocal)[-1] / float(sr):.1f}")
@@ -262,6 +272,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         out["note"] = res["note"]
     if smart:       # `:1341-1347`, and the bar analysis behind the cuts
         for key in ("use_vocal_preprocessing", "bpm", "bar_duration_s", "density", "silence_boundaries", "bar_energies", "bar_types"):
+            out[key] = res.get(key)
+    if hybrid:      # `result_builder.add_hybrid_metadata` (`result_builder.py:100-116`), and what the strategy counted
+        for key in ("segment_lib_flags", "lib_segment_count", "hybrid_config", "beat_analysis", "strategy", "strategy_metadata"):
             out[key] = res.get(key)
     if res.get("boundary_detection") is not None:
         out["boundary_detection"] = res["boundary_detection"]
@@ -414,6 +427,9 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
         manifest["smart_segmentation"] = {"method": result.get("method"), "bpm": result.get("bpm"),
                                           "bar_duration_s": result.get("bar_duration_s"), "density": result.get("density"),
                                           "silence_boundaries": result.get("silence_boundaries", [])}
+    if str(mode) == "hybrid_mdd" and result.get("success"):                               # `hybrid_mdd` results, passed through
+        for key in ("segment_lib_flags", "lib_segment_count", "hybrid_config", "beat_analysis", "strategy"):
+            manifest[key] = result.get(key)
     return manifest
 
 

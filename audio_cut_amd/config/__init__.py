@@ -93,6 +93,18 @@ DEFAULTS: Dict[str, Any] = {
         "energy_analysis": {"hop_length": 512, "chorus_percentile": 60, "chorus_peak_percentile": 80},
         "beat": {"time_signature": 4},
     },
+    # mode `hybrid_mdd` (`expert.yaml:145-169`)
+    "hybrid_mdd": {
+        "beat_cut_density": "medium", "lib_alignment": "snap_to_beat", "snap_tolerance_ms": 200, "vad_protection": True,
+        "chorus_force_snap": False,
+        "density_presets": {
+            "low": {"enable_beat_cuts": True, "energy_percentile": 90, "bars_per_cut": 4},
+            "medium": {"enable_beat_cuts": True, "energy_percentile": 60, "bars_per_cut": 2},
+            "high": {"enable_beat_cuts": True, "energy_percentile": 40, "bars_per_cut": 1},
+        },
+        "beat_detection": {"hop_length": 512, "time_signature": 4, "snap_to_pause_ms": 300},
+        "labeling": {"lib_suffix": "_lib"},
+    },
 }
 
 _runtime: Dict[str, Any] = {}
@@ -183,6 +195,30 @@ def get_librosa_onset_config() -> Dict[str, Any]:
         "density_custom": base.get("density_custom", {"enable": False, "verse_bars": 4, "chorus_bars": 2}),
         "energy_analysis": base.get("energy_analysis", {"hop_length": 512, "chorus_percentile": 60, "chorus_peak_percentile": 80}),
         "beat": base.get("beat", {"time_signature": 4}),
+    }
+
+
+def get_hybrid_mdd_config(density_override: Any = None) -> Dict[str, Any]:
+    """`get_hybrid_mdd_config` (`config_manager.py:605-669`): `density_override` > environment > the `hybrid_mdd` section > the
+    reference's literal defaults.  A density without a preset takes the `medium` preset (and keeps its own name)."""
+    base = get_config("hybrid_mdd", {}) or {}
+    density = density_override or _env_override(base.get("beat_cut_density", "medium"), "AUDIOCUT_HYBRID_DENSITY", str)
+    presets = base.get("density_presets", {})
+    preset = presets.get(density, presets.get("medium", {}))
+    truthy = lambda x: str(x).lower() in ("true", "1", "yes")
+    beat = base.get("beat_detection", {})
+    return {
+        "density": density,
+        "enable_beat_cuts": preset.get("enable_beat_cuts", True),
+        "energy_percentile": preset.get("energy_percentile", 70),
+        "bars_per_cut": preset.get("bars_per_cut", 2),
+        "lib_alignment": _env_override(base.get("lib_alignment", "snap_to_beat"), "AUDIOCUT_HYBRID_LIB_ALIGNMENT", str),
+        "snap_tolerance_ms": _env_override(base.get("snap_tolerance_ms", 300), "AUDIOCUT_SNAP_TOLERANCE_MS", int),
+        "vad_protection": _env_override(base.get("vad_protection", True), "AUDIOCUT_VAD_PROTECTION", truthy),
+        "chorus_force_snap": _env_override(base.get("chorus_force_snap", False), "AUDIOCUT_CHORUS_FORCE_SNAP", truthy),
+        "beat_detection": {"hop_length": beat.get("hop_length", 512), "time_signature": beat.get("time_signature", 4),
+                           "snap_to_pause_ms": beat.get("snap_to_pause_ms", 300)},
+        "labeling": {"lib_suffix": base.get("labeling", {}).get("lib_suffix", "_lib")},
     }
 
 

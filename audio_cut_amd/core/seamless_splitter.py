@@ -53,7 +53,7 @@ PRECISION_GUARD_P95_MS = 220.0
 
 
 class SeamlessSplitter:
-    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr", "librosa_onset")
+    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr", "librosa_onset", "hybrid_mdd")
 
     def __init__(self, sample_rate: int = 44100, *, separator: Optional[EnhancedVocalSeparator] = None,
                  device: Optional[str] = None) -> None:
@@ -75,7 +75,7 @@ class SeamlessSplitter:
 
     # ------------------------------------------------------------------------------------------
     def split_track(self, original_audio: np.ndarray, mode: str = "v2.2_mdd", *, audio_dev=None, separation_gate=None,
-                    unet_stream=None, beat_analysis: bool = False) -> Dict:
+                    unet_stream=None, beat_analysis: bool = False, hybrid_density: Optional[str] = None) -> Dict:
         """Steps 2-9 of SURVEY.md §3.1 on an in-memory mono float32 track at `sample_rate`.
         `separation_gate` (a lock shared by the workers of a `batch.TrackPipeline`) and `unet_stream` (the pipeline's one U-Net
         stream): with both, this track's separation is queued on that stream under the lock and the lock is released as soon as it is
@@ -87,7 +87,9 @@ class SeamlessSplitter:
         `instrumental_track_stereo` ([2, N]) and `mono_mix`.  Stereo tracks are not taken with a gate or U-Net stream.
         `beat_analysis=True` adds a `"beat_analysis"` block (tempo, bars, per-bar energy / centroid / bandwidth, high-energy and
         chorus bars: `_beat_analysis_block`) to the result of every mode that builds a feature cache - all but `librosa_onset`,
-        which reports its own bar analysis.  Off, nothing is launched for it."""
+        which reports its own bar analysis, and `hybrid_mdd`, which always reports the one its cuts were taken from.  Off, nothing
+        is launched for it.
+        `hybrid_density` ("low" / "medium" / "high") overrides `hybrid_mdd.beat_cut_density` for a `hybrid_mdd` track."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
         sr = self.sample_rate
@@ -97,6 +99,10 @@ class SeamlessSplitter:
             if separation_gate is not None or unet_stream is not None:
                 raise ValueError("librosa_onset tracks are split one at a time (no separation gate / U-Net stream)")
             return self._split_librosa_onset(original_audio, audio_dev)
+        if mode == "hybrid_mdd":
+            if separation_gate is not None or unet_stream is not None:
+                raise ValueError("hybrid_mdd tracks are split one at a time (no separation gate / U-Net stream)")
+            return self._split_hybrid_mdd(original_audio, audio_dev, hybrid_density)
         stereo = np.ndim(original_audio) == 2
         t0 = time.perf_counter()
         sep: SeparationResult = self.separator.separate_for_detection(original_audio, gpu_context=None, audio_dev=audio_dev,
@@ -201,7 +207,7 @@ class SeamlessSplitter:
         return result
 
     # ---- optional beat / bar analysis block (reference `audio_cut.analysis.beat_analyzer`, `chorus_regions`) -----------
-    def _beat_analysis_queue(self, mono_mix: np.ndarray, state: Dict):
+    def _beat_analysis_queue(self, mono_mix: np.ndarray, state: Dict, hop_length: Optional[int] = None):
         """Queue the RMS and centroid / bandwidth passes over the resident mix on a stream of their own, right after the
         separation: they run beside the detection tail, which is bound by the host, instead of in front of it."""
         import torch
@@ -213,7 +219,7 @@ class SeamlessSplitter:
         side = torch.cuda.Stream(device=hip.device)
         side.wait_stream(main)                                  # the mix is written on the main stream
         with torch.cuda.stream(side):
-            series = queue_frame_series(hip, mix_dev, self.sample_rate, self.beat_analyzer.hop_length)
+            series = queue_frame_series(hip, mix_dev, self.sample_rate, hop_length or self.beat_analyzer.hop_length)
             done = torch.cuda.Event()
             done.record()
         mix_dev.record_stream(side)
@@ -363,6 +369,220 @@ class SeamlessSplitter:
                        "segment_spans": spans, "segment_durations": [(hi - lo) / float(sr) for lo, hi in spans],
                        "segment_layout_applied": False, "precision_guard_ok": True,
                        "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": t_fin}})
+        return result
+
+    # ---- mode `hybrid_mdd`: phrase-pause cuts snapped to beats in chorus bars (reference `seamless_splitter.py:1351-1704`) -----------
+    def _hybrid_mdd_base(self, original_audio: np.ndarray, audio_dev=None) -> Dict:
+        """The `v2.2_mdd` result `hybrid_mdd` builds on: its `cuts_samples` are the MDD cut points, and its stems, feature cache
+        and device state are reused - ONE separation, where the reference separates for the stems and again inside its MDD run."""
+        return self.split_track(original_audio, "v2.2_mdd", audio_dev=audio_dev)
+
+    def _quiet_gate(self, hip, gate_dev, times: Sequence[float], guard_win_ms: float, guard_db: float) -> Dict:
+        """`is_quiet_vocal_window` (`strategies/base.py:160-200`) for all of `times` at once: one `ac_quiet_gate_meansq` launch over
+        the resident stem, one download.  -> the decisions by centre sample, and the numbers they were taken on."""
+        from ..cutting import hybrid_strategies as HS
+        sr = self.sample_rate
+        half_win = HS.gate_half_window(sr, guard_win_ms)
+        centers = sorted({HS.gate_center(float(t), sr) for t in times})
+        block_ms, point_ms, count = hip.quiet_gate(gate_dev, half_win, np.asarray(centers, dtype=np.int64))
+        floor_db, point_db, quiet = HS.gate_decisions(block_ms, point_ms, count, guard_db)
+        return {"half_win": half_win, "floor_db": floor_db, "centers": centers, "point_db": [float(v) for v in point_db],
+                "point_count": [int(c) for c in count], "quiet": {c: bool(q) for c, q in zip(centers, quiet)}}
+
+    @staticmethod
+    def _remap_lib_flags_to_refined_cuts(raw_cut_points: Sequence[int], raw_lib_flags: Sequence[bool],
+                                         refined_cut_points: Sequence[int]) -> List[bool]:
+        """`:2485-2513`: a refined segment takes the flag of the raw segment whose END is nearest to its own end; a segment that
+        ends at the end of the track, or whose nearest raw end is the end of the track, is never `_lib`."""
+        raw_points = list(raw_cut_points)
+        refined_points = list(refined_cut_points)
+        if len(refined_points) < 2:
+            return []
+        if len(raw_points) < 2:
+            return [False] * (len(refined_points) - 1)
+        raw_end_flags = []
+        for idx, raw_end in enumerate(raw_points[1:]):
+            raw_end_flags.append((int(raw_end), bool(raw_lib_flags[idx]) if idx < len(raw_lib_flags) else False))
+        remapped: List[bool] = []
+        for refined_end in refined_points[1:]:
+            nearest_raw_end, nearest_flag = min(raw_end_flags, key=lambda item: abs(int(refined_end) - item[0]))
+            if int(refined_end) == raw_points[-1] or nearest_raw_end == raw_points[-1]:
+                remapped.append(False)
+            else:
+                remapped.append(nearest_flag)
+        return remapped
+
+    def _hybrid_micro_merge(self, cut_points: Sequence[int], lib_flags: Sequence[bool], micro_merge_s: float):
+        """`:1512-1560`: a segment shorter than `micro_merge_s` that is neither the last one nor `_lib` joins the segment after
+        it, and the run it joins loses its flag.  -> (cut points, flags), the inputs themselves when nothing merged."""
+        final_cut_points, lib_cut_flags = list(cut_points), list(lib_flags)
+        if not (micro_merge_s > 0 and len(final_cut_points) > 2):
+            return final_cut_points, lib_cut_flags
+        merged_cut_points: List[int] = [final_cut_points[0]]
+        merged_lib_flags: List[bool] = []
+        current_segment_was_merged = False
+        for i in range(len(final_cut_points) - 1):
+            duration_s = (final_cut_points[i + 1] - final_cut_points[i]) / float(self.sample_rate)
+            is_lib_segment = lib_cut_flags[i] if i < len(lib_cut_flags) else False
+            if duration_s < micro_merge_s and i < len(final_cut_points) - 2 and not is_lib_segment:
+                current_segment_was_merged = True
+            else:
+                merged_cut_points.append(final_cut_points[i + 1])
+                if current_segment_was_merged:
+                    merged_lib_flags.append(False)
+                elif i < len(lib_cut_flags):
+                    merged_lib_flags.append(lib_cut_flags[i])
+                else:
+                    merged_lib_flags.append(False)
+                current_segment_was_merged = False
+        if len(merged_cut_points) != len(final_cut_points):
+            return merged_cut_points, merged_lib_flags
+        return final_cut_points, lib_cut_flags
+
+    def _split_hybrid_mdd(self, original_audio: np.ndarray, audio_dev=None, density_override: Optional[str] = None) -> Dict:
+        """`_process_hybrid_mdd_split` on an in-memory track: MDD cut points (`_hybrid_mdd_base`) -> beat / bar analysis of the
+        mix -> quiet gate of every beat and bar line on the vocal stem (one launch) -> strategy (`snap_to_beat` / `beat_only`)
+        -> quiet guards on the interior cuts -> `_lib` flags remapped to the guarded cuts -> human / music labels -> micro-merge
+        -> sample-level spans."""
+        from ..config import get_hybrid_mdd_config
+        from ..cutting import hybrid_strategies as HS
+        sr = self.sample_rate
+        hybrid_config = get_hybrid_mdd_config(density_override)
+        energy_percentile = hybrid_config["energy_percentile"]
+        bars_per_cut = hybrid_config["bars_per_cut"]
+        beat_cfg = hybrid_config["beat_detection"]
+        snap_tolerance_ms = hybrid_config["snap_tolerance_ms"]
+        vad_protection = hybrid_config["vad_protection"]
+        chorus_force_snap = bool(hybrid_config.get("chorus_force_snap", False))
+        guard_db = float(get_config("quality_control.enforce_quiet_cut.guard_db", 2.5))
+        guard_win_ms = float(get_config("quality_control.enforce_quiet_cut.win_ms", 80))
+        lib_alignment = hybrid_config.get("lib_alignment", "snap_to_beat")
+        stereo = np.ndim(original_audio) == 2
+
+        t0 = time.perf_counter()
+        base = self._hybrid_mdd_base(original_audio, audio_dev)
+        t_base = time.perf_counter() - t0
+        if base.get("success"):
+            mdd_cut_points_samples = [int(c) for c in base.get("cuts_samples", [])]
+        else:                                               # `:1416-1424`
+            if lib_alignment == "snap_to_beat":
+                logger.warning("[HYBRID_MDD] MDD failed for snap_to_beat; fallback to beat_only")
+                lib_alignment = "beat_only"
+            if lib_alignment == "beat_only":
+                mdd_cut_points_samples = []
+            else:
+                return base
+        t1 = time.perf_counter()
+        if stereo:
+            mono = base.get("mono_mix")
+            if mono is None:
+                mono = (original_audio[0] + original_audio[1]) * np.float32(0.5)
+        else:
+            mono = original_audio
+        state = dict(base.get("device_state") or {})
+        hip = state.get("hip") or self._context()
+        n = len(mono)
+        if state.get("mix") is None:
+            state["mix"] = hip.to_device(np.ascontiguousarray(mono, dtype=np.float32))
+        stem = base.get("vocal_track")
+        vocal_track = stem if stem is not None else mono       # `:1403`: the guards and labels read the mix without a stem
+        vocal_dev = state.get("vocal") if stem is not None else state["mix"]
+        if vocal_dev is None:
+            vocal_dev = hip.to_device(np.ascontiguousarray(vocal_track, dtype=np.float32))
+        cache = base.get("feature_cache")
+
+        pending = self._beat_analysis_queue(mono, state, int(beat_cfg["hop_length"]))
+        import torch
+        _, mix_dev, series, done = pending
+        torch.cuda.current_stream().wait_event(done)
+        beat_result = self.beat_analyzer.analyze(mono, sr=sr, hop_length=beat_cfg["hop_length"], time_signature=beat_cfg["time_signature"],
+                                                 energy_percentile=energy_percentile, feature_cache=cache, ctx=hip, audio_dev=mix_dev,
+                                                 frame_series=series)
+        gate = self._quiet_gate(hip, vocal_dev, [float(t) for t in beat_result.beat_times] + [float(t) for t in beat_result.bar_times],
+                                guard_win_ms, guard_db)
+
+        min_segment_s = float((get_config("segment_layout", {}) or {}).get("soft_min_s", 2.0))
+        micro_merge_s = float((get_config("segment_layout", {}) or {}).get("micro_merge_s", 2.0))
+        context = HS.SegmentationContext(
+            audio=mono, sample_rate=sr, tempo=beat_result.tempo, beat_times=beat_result.beat_times, bar_times=beat_result.bar_times,
+            bar_duration=beat_result.bar_duration, mdd_cut_points_samples=mdd_cut_points_samples,
+            energy_threshold=beat_result.energy_threshold, bar_energies=beat_result.bar_energies,
+            bar_spectral_centroids=beat_result.bar_spectral_centroids, bar_spectral_bandwidths=beat_result.bar_spectral_bandwidths,
+            quiet_gate=gate["quiet"],
+            config={"density": hybrid_config["density"], "enable_beat_cuts": hybrid_config["enable_beat_cuts"],
+                    "bars_per_cut": bars_per_cut, "min_segment_s": min_segment_s, "energy_percentile": energy_percentile,
+                    "snap_to_pause_ms": beat_cfg["snap_to_pause_ms"], "snap_tolerance_ms": snap_tolerance_ms,
+                    "vad_protection": vad_protection, "chorus_force_snap": chorus_force_snap, "guard_db": guard_db,
+                    "guard_win_ms": guard_win_ms})
+        strategies = {"beat_only": HS.BeatOnlyStrategy(), "snap_to_beat": HS.SnapToBeatStrategy()}
+        strategy = strategies.get(lib_alignment)
+        if strategy is None:
+            logger.warning("[HYBRID_MDD] Unknown lib_alignment=%s, fallback to snap_to_beat", lib_alignment)
+            lib_alignment = "snap_to_beat"
+            strategy = strategies[lib_alignment]
+        seg_result = strategy.generate_cut_points(context)
+        final_cut_points = list(seg_result.cut_points_samples)
+        lib_cut_flags = list(seg_result.lib_flags)
+        t_det = time.perf_counter() - t1
+
+        t2 = time.perf_counter()
+        raw_strategy_cut_points, raw_strategy_lib_flags = list(final_cut_points), list(lib_cut_flags)
+        self._last_guard_adjustments_raw = []               # the guard statistics below are this mode's, not the MDD run's
+        self._last_suppressed_cut_points = []
+        if len(raw_strategy_cut_points) > 2:
+            refined = self._finalize_and_filter_cuts_v2([(s / float(sr), 1.0) for s in raw_strategy_cut_points[1:-1]], mono,
+                                                        pure_vocal_audio=vocal_track, mix_dev=state["mix"], vocal_dev=vocal_dev)
+            self._last_suppressed_cut_points = list(refined.suppressed_points or [])
+            guarded_cut_points = [int(b) for b in refined.sample_boundaries]
+            if len(guarded_cut_points) >= 2:
+                final_cut_points = guarded_cut_points
+                lib_cut_flags = self._remap_lib_flags_to_refined_cuts(raw_strategy_cut_points, raw_strategy_lib_flags, final_cut_points)
+        refined_cut_points, refined_lib_flags = list(final_cut_points), list(lib_cut_flags)
+        segment_vocal_flags = self._classify_segments_vocal_presence(vocal_track, final_cut_points, vocal_dev=vocal_dev)
+        merged_points, merged_flags = self._hybrid_micro_merge(final_cut_points, lib_cut_flags, micro_merge_s)
+        if len(merged_points) != len(final_cut_points):
+            final_cut_points, lib_cut_flags = merged_points, merged_flags
+            segment_vocal_flags = self._classify_segments_vocal_presence(vocal_track, final_cut_points, vocal_dev=vocal_dev)
+        spans, returned_flags = self._sample_level_spans(n, final_cut_points, segment_vocal_flags)
+        spans = list(spans)
+        t_fin = time.perf_counter() - t2
+
+        kept = list(self._last_guard_adjustments_raw)
+        stats = self._guard_shift_stats(kept)
+        t_sep = float((base.get("timings") or {}).get("separate_s", 0.0))
+        if lib_alignment == "beat_only":
+            hybrid_meta = {"density": hybrid_config["density"], "lib_alignment": "beat_only", "bars_per_cut": bars_per_cut}
+            strategy_metadata = {"vad_blocked": seg_result.metadata["vad_blocked"]}
+        else:
+            hybrid_meta = {"density": hybrid_config["density"], "lib_alignment": "snap_to_beat", "bars_per_cut": bars_per_cut,
+                           "snap_tolerance_ms": snap_tolerance_ms, "vad_protection": vad_protection}
+            strategy_metadata = {"snap_stats": dict(seg_result.metadata["snap_stats"])}
+        result: Dict = {
+            "success": True, "mode": "hybrid_mdd", "method": f"hybrid_mdd_{lib_alignment}", "strategy": lib_alignment,
+            "gpu_meta": dict(base.get("gpu_meta") or {}), "separation_confidence": base.get("separation_confidence"),
+            "backend_used": base.get("backend_used"), "vad_segments": base.get("vad_segments"), "feature_cache": cache,
+            "vocal_track": stem, "instrumental_track": base.get("instrumental_track"), "device_state": state,
+            "mdd_success": bool(base.get("success")), "mdd_cut_points_samples": list(mdd_cut_points_samples),
+            "strategy_cut_points_samples": raw_strategy_cut_points, "strategy_lib_flags": raw_strategy_lib_flags,
+            "sample_boundaries": refined_cut_points, "refined_lib_flags": refined_lib_flags,
+            "cuts_samples": list(final_cut_points), "cuts_sec": [c / float(sr) for c in final_cut_points],
+            "segment_vocal_flags": list(returned_flags if returned_flags else segment_vocal_flags),
+            "segment_spans": spans, "segment_durations": [(hi - lo) / float(sr) for lo, hi in spans],
+            "segment_lib_flags": list(lib_cut_flags), "lib_segment_count": sum(1 for f in lib_cut_flags if f),
+            "lib_suffix": hybrid_config["labeling"]["lib_suffix"],
+            "hybrid_config": hybrid_meta, "strategy_metadata": strategy_metadata,
+            "beat_analysis": {"bpm": beat_result.tempo, "bar_duration_s": beat_result.bar_duration, "num_bars": len(beat_result.bar_times)},
+            "beat_times": [float(t) for t in beat_result.beat_times], "bar_times": [float(t) for t in beat_result.bar_times],
+            "bar_energies": list(beat_result.bar_energies), "bar_spectral_centroids": list(beat_result.bar_spectral_centroids),
+            "bar_spectral_bandwidths": list(beat_result.bar_spectral_bandwidths), "quiet_gate": gate,
+            "segment_layout_applied": False, "suppressed_cut_points_sec": [float(c.t) for c in self._last_suppressed_cut_points],
+            "guard_adjustments": kept, "guard_shift_stats": stats,
+            "precision_guard_ok": bool(stats["avg_shift_ms"] <= PRECISION_GUARD_AVG_MS and stats["p95_shift_ms"] <= PRECISION_GUARD_P95_MS),
+            "precision_guard_threshold_ms": {"avg": PRECISION_GUARD_AVG_MS, "p95": PRECISION_GUARD_P95_MS},
+            "timings": {"separate_s": t_sep, "detect_s": max(0.0, t_base - t_sep) + t_det, "finalize_s": t_fin}}
+        if stereo:
+            result.update({"vocal_track_stereo": base.get("vocal_track_stereo"),
+                           "instrumental_track_stereo": base.get("instrumental_track_stereo"), "mono_mix": mono})
         return result
 
     # ------------------------------------------------------------------------------------------
