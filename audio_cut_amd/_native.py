@@ -49,6 +49,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so beat ABI version mismatch")
     if lib.ac_hybrid_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so hybrid ABI version mismatch")
+    if lib.ac_export_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so export ABI version mismatch")
     _lib = lib
     return lib
 
@@ -141,10 +143,16 @@ HYBRID_SIGNATURES = {
     "ac_quiet_gate_meansq": (C.c_int, [_P, _P, _I64, _I64, _P, _I, _P, _I64, _P, _P, _P]),
 }
 
+# include/audiocut_hip_export.h: the `vocal_separation` mode's stem writer, exported by the same library and versioned on its own
+EXPORT_SIGNATURES = {
+    "ac_export_abi_version": (C.c_int, []),
+    "ac_mdx_assemble_pcm24": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+}
+
 
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
-                              *HYBRID_SIGNATURES.items()):
+                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -884,6 +892,29 @@ class Context:
             _check(self.lib.ac_mdx_chunk_vocal(self._h, _ptr(wave), _ptr(chunk_len), _ptr(out_offset), _ptr(item_base),
                                                chunk_len.numel(), _ptr(out), _stream()))
         return out
+
+    ASSEMBLE_PCM24_MAX_PARTIALS = 4096
+
+    def mdx_assemble_pcm24(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base):
+        """-> (stem_pcm, rest_pcm, partials): the network's stem and the mix minus it as finished little-endian PCM_24 bytes on the
+        device (uint8 [3 n] for a mono track, [6 n] with frames interleaved L, R for a stereo one: the stems `mdx_assemble_ola`
+        gives, converted as `pack_pcm24` converts them, with no float stem in between) and float64 [3, parts] partial sums of
+        squares of the mono stem, the mono rest and the mono mix, to be added in index order on the host.  One launch
+        (include/audiocut_hip_export.h)."""
+        stereo = self._chk_track(track)
+        n = int(track.shape[-1])
+        if n == 0:
+            raise NativeError("mdx_assemble_pcm24: empty track")
+        ch = 2 if stereo else 1
+        groups = -(-n * ch // 4)
+        parts = min(self.ASSEMBLE_PCM24_MAX_PARTIALS, -(-groups // 256))
+        stem = torch.empty(3 * ch * n, dtype=torch.uint8, device=self.device)
+        rest = torch.empty(3 * ch * n, dtype=torch.uint8, device=self.device)
+        partials = torch.empty((3, parts), dtype=torch.float64, device=self.device)
+        _check(self.lib.ac_mdx_assemble_pcm24(self._h, _ptr(track), n, ch, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len), _ptr(eff_start),
+                                              _ptr(eff_end), _ptr(item_base), chunk_start.numel(), _ptr(stem), _ptr(rest), _ptr(partials),
+                                              parts, _stream()))
+        return stem, rest, partials
 
     # -- U-Net layers (NCHW float32; `in_amax` / `out_amax`: per-item max |x| of the input / output tensor, include/audiocut_hip.h) --
     AMAX_ROWS = 1       # AC_AMAX_ROWS: rows of the time axis per amax entry (one maximum per item and time row)

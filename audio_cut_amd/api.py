@@ -5,7 +5,8 @@ SegmentManifest.
 Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, `librosa_onset`
 (bar-aligned smart segmentation: mix segments by default, vocal segments on request, no full stems) and
 `hybrid_mdd` (phrase-pause cuts snapped to beats in chorus bars: mix and vocal segments named `..._lib_D.D` where a segment ends on
-a beat, and the full vocal).
+a beat, and the full vocal) and `vocal_separation` (the two stems and nothing else: `<name>_vocal_D.D.wav` and
+`<name>_instrumental_D.D.wav`, no detection, no segments).
 Loader: PCM WAV / .npy, channel mean like `librosa.load(mono=True)`; a file whose rate differs from `audio.sample_rate`
 is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
@@ -123,6 +124,65 @@ def _normalize_export_plan(export_types: Optional[Sequence[str]]) -> list:
     return plan
 
 
+def _vocal_separation_plan(export_types: Optional[Sequence[str]]) -> set:
+    """Mode `vocal_separation`: `_normalize_export_plan(export_plan, default=('full_vocal', 'full_instrumental'))`
+    (`seamless_splitter.py:107-153,975-978`).  No plan, an empty one or one of blanks is the default; `all` adds the default, `none`
+    empties the plan; the reference's aliases are taken; a segment kind stays in the plan and writes nothing (`:984,996`).  A token
+    that names no kind is refused as in the other modes."""
+    default = ("full_vocal", "full_instrumental")
+    alias = {"vocal": "full_vocal", "vocal_full": "full_vocal", "instrumental": "full_instrumental",
+             "instrumental_full": "full_instrumental", "human_segments": "vocal_segments", "human": "vocal_segments",
+             "music_segments": "mix_segments", "music": "mix_segments"}
+    allowed = ("mix_segments", "vocal_segments", "full_vocal", "full_instrumental")
+    if export_types is None:
+        return set(default)
+    flags: set = set()
+    for item in export_types:
+        key = "" if item is None else str(item).strip().lower()
+        if not key:
+            continue
+        if key == "none":
+            return set()
+        if key == "all":
+            flags.update(default)
+            continue
+        key = alias.get(key, key)
+        if key not in allowed:
+            raise ValueError(f"unknown export type {item!r}; choose from {allowed}")
+        flags.add(key)
+    return flags or set(default)
+
+
+def _export_vocal_separation(res: Mapping[str, Any], in_path: Path, out_dir: Path, export_types: Optional[Sequence[str]], sr: int,
+                             t_start: float) -> Dict[str, Any]:
+    """The export half of `_process_vocal_separation_only` (`seamless_splitter.py:975-1036`): `<name>_vocal_<seconds:.1f>.wav` and
+    `<name>_instrumental_<seconds:.1f>.wav` from the PCM_24 bytes the separation produced, and the reference's result dict."""
+    import time
+    from .utils.audio_export import PackedTrack, SegmentExporter
+    plan = _vocal_separation_plan(export_types)
+    pcm = res["stem_pcm24"]
+    seconds = int(pcm["n"]) / float(sr)
+    exporter = SegmentExporter(sr)
+    files: Dict[str, Optional[str]] = {"vocal": None, "instrumental": None}
+    saved = []
+    for kind in ("vocal", "instrumental"):
+        if f"full_{kind}" in plan and pcm.get(kind) is not None:      # no instrumental: the reference logs it and goes on (`:1007-1008`)
+            track = PackedTrack.from_pcm24(pcm[kind], int(pcm["n"]), int(pcm["channels"]), sr)
+            files[kind] = exporter.export_full_track(track, out_dir / f"{in_path.stem}_{kind}_{seconds:.1f}")
+            saved.append(files[kind])
+    out: Dict[str, Any] = {
+        "success": True, "mode": "vocal_separation", "method": res["method"], "num_segments": 0, "saved_files": saved,
+        "mix_segment_files": [], "vocal_segment_files": [], "full_vocal_file": files["vocal"],
+        "full_instrumental_file": files["instrumental"], "export_plan": sorted(plan), "backend_used": res.get("backend_used"),
+        "separation_confidence": res.get("separation_confidence"), "processing_time": time.time() - t_start,
+        "segment_durations": [], "guard_shift_stats": dict(res["guard_shift_stats"]),
+        "precision_guard_ok": bool(res["precision_guard_ok"]), "precision_guard_threshold_ms": dict(res["precision_guard_threshold_ms"]),
+        "input_file": str(in_path), "output_dir": str(out_dir), "sample_rate": sr, "timings": res.get("timings", {}),
+    }
+    out.update(res.get("gpu_meta", {}))
+    return out
+
+
 def separate_and_segment(*, input_uri: str, export_dir: str, mode: Optional[str] = None, segments: Optional[Any] = None,
                          alignment: Optional[Any] = None, device: Optional[str] = None,
                          export_types: Optional[Sequence[str]] = None, layout: Optional[Any] = None,
@@ -205,6 +265,8 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     if not res.get("success", True):                    # `split_audio_seamlessly`'s failure result (`:231-233`): nothing is written
         return {"success": False, "error": res.get("error"), "input_file": str(in_path), "mode": mode,
                 "timings": res.get("timings", {}), "processing_time": time.time() - t_start}
+    if mode == "vocal_separation":
+        return _export_vocal_separation(res, in_path, out_dir, export_types, sr, t_start)
     smart = mode == "librosa_onset"
     hybrid = mode == "hybrid_mdd"
     single = bool(res.get("single_segment"))            # `_create_single_segment_result`: only the mix, no duration tag

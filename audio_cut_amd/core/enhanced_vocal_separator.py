@@ -43,7 +43,7 @@ logger = logging.getLogger(__name__)
 
 @dataclass
 class SeparationResult:
-    vocal_track: np.ndarray
+    vocal_track: Optional[np.ndarray]
     instrumental_track: Optional[np.ndarray]
     separation_confidence: float
     backend_used: str
@@ -59,6 +59,9 @@ class SeparationResult:
     mono_mix: Optional[np.ndarray] = None
     vocal_track_stereo: Optional[np.ndarray] = None
     instrumental_track_stereo: Optional[np.ndarray] = None
+    # extension, `separate_only`: {"vocal": uint8 PCM_24 bytes, "instrumental": the same or None, "channels": 1 | 2, "n": N};
+    # stereo frames are interleaved L, R as `PackedTrack` lays them out
+    stem_pcm24: Optional[Dict[str, object]] = None
 
 
 def compute_vocal_presence_markers(hip: "_native.Context", vocal_dev: torch.Tensor, sr: int) -> Dict:
@@ -332,6 +335,76 @@ class EnhancedVocalSeparator:
                           "instrumental_track_stereo": inst_st_h.numpy() if has_inst else None}
         return vocal, inst, cache, vad_segments, markers, confidence, state, stereo_out
 
+    # ------------------------------------------------------------------------------------------
+    def separate_only(self, audio: np.ndarray, *, gpu_context: Optional[PipelineContext] = None,
+                      audio_dev: Optional[torch.Tensor] = None) -> SeparationResult:
+        """Mode `vocal_separation` (reference `seamless_splitter.py:958-1036`): the separation of `separate_for_detection` and
+        nothing of what detection needs.  The iSTFT output goes straight to 24-bit PCM (`ac_mdx_assemble_pcm24`): the result
+        carries `stem_pcm24` and the confidence, no float stems, no feature cache, no VAD segments, no markers.  `audio` is a mono
+        [N] or a planar stereo [2, N] float32 track; a stereo track gives two-channel stems."""
+        backend = self._primary_backend
+        if backend is None:
+            raise RuntimeError("separator backend not initialised")
+        if not isinstance(backend, MDX23HipBackend):
+            raise RuntimeError("only MDX23HipBackend drives the batched device path")
+        stereo = np.ndim(audio) == 2
+        if stereo and np.shape(audio)[0] != 2:
+            raise ValueError("a stereo track is a planar (2, N) array")
+        start = time.time()
+        ctx = self._ensure_pipeline_context(audio, gpu_context)
+        try:
+            pcm, confidence = self._separate_to_pcm24(audio, backend, ctx, audio_dev)
+        except Exception as exc:
+            ctx.mark_failure("separation", str(exc))
+            raise
+        return SeparationResult(
+            vocal_track=None, instrumental_track=None, separation_confidence=confidence, backend_used=type(backend).__name__,
+            processing_time=time.time() - start, quality_metrics={}, feature_cache=None, vad_segments=[], gpu_meta=ctx.to_meta(),
+            pipeline_used=ctx.enabled, stem_pcm24=pcm)
+
+    def _separate_to_pcm24(self, audio, backend: MDX23HipBackend, gpu_context: PipelineContext, audio_dev):
+        sr = self.sample_rate
+        hip = backend.hip
+        stereo = np.ndim(audio) == 2
+        total = int(np.shape(audio)[-1])
+        timings: Dict[str, float] = {}
+        t0 = time.perf_counter()
+        if audio_dev is not None:
+            if tuple(audio_dev.shape) != tuple(np.shape(audio)) or not audio_dev.is_contiguous() or audio_dev.dtype != torch.float32:
+                raise ValueError("audio_dev must be the contiguous float32 device copy of `audio`")
+            track_dev = audio_dev
+        else:
+            track_dev = hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+        torch.cuda.current_stream(hip.device).synchronize()
+        h2d_ms = (time.perf_counter() - t0) * 1000.0
+
+        sep = backend.separate_track(track_dev, sr, gpu_context.plans, timings, defer_sync=True, export_pcm24=True)
+        t1 = time.perf_counter()
+        vocal_h = torch.empty(sep.vocal.shape, dtype=torch.uint8, pin_memory=True)
+        inst_h = torch.empty(sep.instrumental.shape, dtype=torch.uint8, pin_memory=True)
+        vocal_h.copy_(sep.vocal, non_blocking=True)
+        inst_h.copy_(sep.instrumental, non_blocking=True)
+        gpu_context.capture_device_metrics()      # as in the detection path: taken while the host waits for the U-Net anyway
+        sep.finish()
+        ve, ie, me = (float(np.sum(row)) / float(total) for row in sep.energy_partials.cpu().numpy())    # partials added in index order
+        torch.cuda.current_stream(hip.device).synchronize()
+        dtoh_ms = (time.perf_counter() - t1) * 1000.0
+        has_inst = ie > 0.0                       # `:458` (`np.any(instrumental)`)
+        confidence = self._confidence_from_energies(ve, ie if has_inst else None, me)
+
+        gm = gpu_context.gpu_meta
+        gm["gpu_pipeline_processed_chunks"] = len(sep.chunk_ranges)
+        gm["gpu_pipeline_used"] = bool(gpu_context.enabled)
+        gm["gpu_pipeline_h2d_ms"] = float(h2d_ms)
+        gm["gpu_pipeline_dtoh_ms"] = float(dtoh_ms)
+        gm["gpu_pipeline_compute_ms"] = float(timings.get("stft_ms", 0.0) + timings.get("unet_ms", 0.0) + timings.get("istft_ms", 0.0))
+        gm["gpu_pipeline_peak_mem_bytes"] = float(torch.cuda.max_memory_allocated(hip.device))
+        gm["gpu_pipeline_chunk_invocations"] = len(sep.chunk_ranges)
+        gm["mdx23_output_type"] = backend.get_output_type()
+        gm["gpu_pipeline_stage_ms"] = dict(timings)
+        pcm = {"vocal": vocal_h.numpy(), "instrumental": inst_h.numpy() if has_inst else None, "channels": 2 if stereo else 1, "n": total}
+        return pcm, confidence
+
     def _side_stream(self, hip) -> "torch.cuda.Stream":
         """A second HIP stream (high priority) for the mix-only feature path that overlaps the U-Net."""
         st = getattr(self, "_side", None)
@@ -345,9 +418,17 @@ class EnhancedVocalSeparator:
         """`:490-501` with the three mean squares reduced on the GPU (float64 partials)."""
         ve = hip.mean_square(vocal_dev) if vocal_dev.numel() else 0.0
         me = hip.mean_square(mix_dev) if mix_dev.numel() else 1e-8
-        ratio = float(np.clip(ve / (me + 1e-8), 0.0, 1.0))
+        ie = None
         if inst_dev is not None and inst_dev.numel():
-            bal = ve / ((hip.mean_square(inst_dev) if inst_energy is None else inst_energy) + 1e-8)
+            ie = hip.mean_square(inst_dev) if inst_energy is None else inst_energy
+        return EnhancedVocalSeparator._confidence_from_energies(ve, ie, me)
+
+    @staticmethod
+    def _confidence_from_energies(ve: float, ie: Optional[float], me: float) -> float:
+        """`:490-501` on the mean squares of the vocal, the instrumental (None: there is none) and the mix."""
+        ratio = float(np.clip(ve / (me + 1e-8), 0.0, 1.0))
+        if ie is not None:
+            bal = ve / (ie + 1e-8)
             return float(np.clip(0.5 * ratio + 0.5 * np.clip(bal / (1.0 + bal), 0.0, 1.0), 0.0, 1.0))
         return float(np.clip(ratio, 0.0, 1.0))
 

@@ -53,7 +53,7 @@ PRECISION_GUARD_P95_MS = 220.0
 
 
 class SeamlessSplitter:
-    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr", "librosa_onset", "hybrid_mdd")
+    SUPPORTED_MODES = ("v2.2_mdd", "v2.1", "vpbd_acoustic", "vpbd_asr", "librosa_onset", "hybrid_mdd", "vocal_separation")
 
     def __init__(self, sample_rate: int = 44100, *, separator: Optional[EnhancedVocalSeparator] = None,
                  device: Optional[str] = None) -> None:
@@ -89,7 +89,8 @@ class SeamlessSplitter:
         chorus bars: `_beat_analysis_block`) to the result of every mode that builds a feature cache - all but `librosa_onset`,
         which reports its own bar analysis, and `hybrid_mdd`, which always reports the one its cuts were taken from.  Off, nothing
         is launched for it.
-        `hybrid_density` ("low" / "medium" / "high") overrides `hybrid_mdd.beat_cut_density` for a `hybrid_mdd` track."""
+        `hybrid_density` ("low" / "medium" / "high") overrides `hybrid_mdd.beat_cut_density` for a `hybrid_mdd` track.
+        Mode `vocal_separation` separates and detects nothing: `_split_vocal_separation`."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
         sr = self.sample_rate
@@ -99,6 +100,12 @@ class SeamlessSplitter:
             if separation_gate is not None or unet_stream is not None:
                 raise ValueError("librosa_onset tracks are split one at a time (no separation gate / U-Net stream)")
             return self._split_librosa_onset(original_audio, audio_dev)
+        if mode == "vocal_separation":
+            if separation_gate is not None or unet_stream is not None:
+                raise ValueError("vocal_separation tracks are separated one at a time (no separation gate / U-Net stream)")
+            if beat_analysis:
+                raise ValueError("vocal_separation builds no feature cache: there is no beat analysis to report")
+            return self._split_vocal_separation(original_audio, audio_dev)
         if mode == "hybrid_mdd":
             if separation_gate is not None or unet_stream is not None:
                 raise ValueError("hybrid_mdd tracks are split one at a time (no separation gate / U-Net stream)")
@@ -205,6 +212,19 @@ class SeamlessSplitter:
                        "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": t_fin}})
         self._beat_analysis_block(beat_pending, original_audio, cache, result)
         return result
+
+    # ---- mode `vocal_separation`: the two stems and nothing else (reference `seamless_splitter.py:958-1036`) ----------
+    def _split_vocal_separation(self, original_audio: np.ndarray, audio_dev=None) -> Dict:
+        """`_process_vocal_separation_only` on an in-memory track: separate, and report the reference's result fields (`:1012-1035`)
+        with no segments and no cuts.  The stems come back as finished PCM_24 bytes (`stem_pcm24`, `separate_only`); the caller
+        writes them (`api._split_and_export`)."""
+        t0 = time.perf_counter()
+        sep: SeparationResult = self.separator.separate_only(original_audio, gpu_context=None, audio_dev=audio_dev)
+        return {"success": True, "mode": "vocal_separation", "method": "vocal_separation_only", "num_segments": 0,
+                "segment_durations": [], "stem_pcm24": sep.stem_pcm24, "backend_used": sep.backend_used,
+                "separation_confidence": sep.separation_confidence, "guard_shift_stats": self._guard_shift_stats([]),
+                "precision_guard_ok": True, "precision_guard_threshold_ms": {"avg": PRECISION_GUARD_AVG_MS, "p95": PRECISION_GUARD_P95_MS},
+                "gpu_meta": dict(sep.gpu_meta or {}), "timings": {"separate_s": time.perf_counter() - t0}}
 
     # ---- optional beat / bar analysis block (reference `audio_cut.analysis.beat_analyzer`, `chorus_regions`) -----------
     def _beat_analysis_queue(self, mono_mix: np.ndarray, state: Dict, hop_length: Optional[int] = None):

@@ -221,3 +221,12 @@ __device__ inline double block_sum_f64_256(double v, double* smem4) {
     __syncthreads();
     return smem4[0] + smem4[1] + smem4[2] + smem4[3];
 }
+
+// ---- float32 -> 24-bit PCM word (ac_pack_pcm24, ac_mdx_assemble_pcm24): libsndfile pcm.c f2let_clip_array, see ac_io.hip ----------
+__device__ inline int pcm24(float v) {
+    const float s = v * 2147483648.0f;                   // libsndfile: normfact = 8.0 * 0x10000000, product in float32
+    if (s >= 2147483647.0f) return 8388607;              // (float)0x7FFFFFFF == 2^31: every s >= 1.0 * 0x7FFFFFFF
+    if (s <= -2147483648.0f) return -8388608;
+    if (!(s == s)) return 0;                             // NaN: lrintf is undefined there; silence
+    return ((int)rintf(s)) >> 8;                         // lrintf (half to even), then the three high bytes
+}

@@ -35,14 +35,6 @@ extern "C" int ac_resample_poly(ac_ctx* ctx, const float* x, int64_t n, int up, 
     return AC_OK;
 }
 
-__device__ inline int pcm24(float v) {
-    const float s = v * 2147483648.0f;                   // libsndfile: normfact = 8.0 * 0x10000000, product in float32
-    if (s >= 2147483647.0f) return 8388607;              // (float)0x7FFFFFFF == 2^31: every s >= 1.0 * 0x7FFFFFFF
-    if (s <= -2147483648.0f) return -8388608;
-    if (!(s == s)) return 0;                             // NaN: lrintf is undefined there; silence
-    return ((int)rintf(s)) >> 8;                         // lrintf (half to even), then the three high bytes
-}
-
 __global__ __launch_bounds__(256) void k_pack_pcm24(const float* __restrict__ x, int64_t n, unsigned char* __restrict__ out) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;       // quad of samples
     const int64_t s0 = q * 4;

@@ -83,6 +83,20 @@ class TrackSeparation:
     instrumental_stereo: Optional[torch.Tensor] = None   # [2, N] f32 for a stereo track, else None
 
 
+@dataclass
+class TrackStemsPcm24:
+    """Device-resident result of `MDX23HipBackend.separate_track(export_pcm24=True)`: the stems as finished PCM_24 bytes."""
+
+    vocal: torch.Tensor            # uint8 [3 * channels * n]; stereo frames interleaved L, R
+    instrumental: torch.Tensor     # uint8 [3 * channels * n]
+    energy_partials: torch.Tensor  # float64 [3, parts]: partial sums of squares of the mono vocal, mono instrumental, mono mix
+    channels: int
+    n: int
+    chunk_ranges: List[Tuple[int, int, int, int]]
+    n_items: int
+    finish: Optional[object] = None
+
+
 def items_per_chunk(chunk_len: int, align_hop: int) -> int:
     """backends.py:277-281,310-312: align to `align_hop`, then pad to a multiple of GEN."""
     aligned = chunk_len + ((-chunk_len) % max(1, align_hop))
@@ -184,7 +198,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
     # -- batched fast path ------------------------------------------------------------------------
     def separate_track(self, track_dev: torch.Tensor, sr: int, plans: Sequence[ChunkPlan],
                        timings: Optional[Dict[str, float]] = None, defer_sync: bool = False, before_launch=None,
-                       unet_stream=None, after_launch=None) -> TrackSeparation:
+                       unet_stream=None, after_launch=None, export_pcm24: bool = False):
         """All chunks of a resident track: STFT -> U-Net -> iSTFT -> stem assembly + OLA, no host bounce.
         Everything is queued on the current stream without a host synchronisation; `defer_sync=True` returns at once
         (the caller overlaps host work and calls `result.finish()` later), otherwise the timings are read before returning.
@@ -194,7 +208,11 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         end); `batch.TrackPipeline` gives every worker the same one, so the separations of consecutive tracks are ordered by
         the stream itself and the next one can be queued while this one still runs - `after_launch` is then called as soon as
         everything is queued (the pipeline's gate only has to keep two tracks' launches from interleaving).
-        `track_dev` is a mono [N] or a planar stereo [2, N] float32 track; a stereo one also fills `vocal_stereo` / `instrumental_stereo`."""
+        `track_dev` is a mono [N] or a planar stereo [2, N] float32 track; a stereo one also fills `vocal_stereo` / `instrumental_stereo`.
+        `export_pcm24=True` (mode `vocal_separation`): the iSTFT output goes through `ac_mdx_assemble_pcm24` instead of the stem
+        assembly and the per-chunk vocals, and a `TrackStemsPcm24` comes back: no float stem is written.  Not with `unet_stream`."""
+        if export_pcm24 and unet_stream is not None:
+            raise ValueError("export_pcm24 tracks are separated one at a time (no U-Net stream)")
         hip = self.hip
         net = self.net
         if track_dev.dim() == 2:
@@ -242,11 +260,14 @@ class MDX23HipBackend(IVocalSeparatorBackend):
                 t.record_stream(unet_stream)
         with (torch.cuda.stream(unet_stream) if unet_stream is not None else contextlib.nullcontext()):
             sep_out = self._queue_separation(track_dev, n_items, step, timings, ranges, offsets,
-                                             (d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets))
+                                             (d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets), export_pcm24)
             if unet_stream is not None:
                 queued = torch.cuda.Event()
                 queued.record()
-        wave, vocal, inst, chunk_vocal, vocal_st, inst_st, events = sep_out
+        if export_pcm24:
+            events = sep_out[-1]
+        else:
+            wave, vocal, inst, chunk_vocal, vocal_st, inst_st, events = sep_out
         if unet_stream is not None:
             if after_launch is not None:
                 after_launch()
@@ -270,11 +291,15 @@ class MDX23HipBackend(IVocalSeparatorBackend):
 
         if not defer_sync:
             finish()
+        if export_pcm24:
+            vocal_pcm, inst_pcm, partials = sep_out[:3]
+            return TrackStemsPcm24(vocal_pcm, inst_pcm, partials, track_dev.dim(), n, ranges, n_items, finish if defer_sync else None)
         return TrackSeparation(vocal, inst, chunk_vocal, [int(o) for o in offsets[:-1]], ranges, n_items,
                                finish if defer_sync else None, vocal_st, inst_st)
 
-    def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables):
-        """Queues STFT -> U-Net -> iSTFT of every sub-batch and the stem assembly on the CURRENT stream; no host synchronisation."""
+    def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables, export_pcm24=False):
+        """Queues STFT -> U-Net -> iSTFT of every sub-batch and the stem assembly on the CURRENT stream; no host synchronisation.
+        `export_pcm24`: the assembly is `ac_mdx_assemble_pcm24` and the result (vocal bytes, instrumental bytes, partials, events)."""
         hip = self.hip
         net = self.net
         d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets = tables
@@ -295,6 +320,11 @@ class MDX23HipBackend(IVocalSeparatorBackend):
             if ev:
                 ev[3].record()
                 events.append(ev)
+        if export_pcm24:        # an instrumental-type network: the two streams, and the first two rows of the partials, change places
+            stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm24(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
+            if self.get_output_type() == "vocal":
+                return stem_pcm, rest_pcm, partials, events
+            return rest_pcm, stem_pcm, partials[[1, 0, 2]], events
         # the network's stem and the mix minus it (for a stereo track the mono stems are the channel means of the stereo ones, in
         # mdx_assemble's order); an instrumental-type network swaps them, and the VAD input becomes the mix minus its stem
         stem, rest, stem_st, rest_st = hip.mdx_assemble_ola(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
@@ -334,4 +364,4 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         return SeparationOutputs(vocal=vocal.astype(np.float32), instrumental=inst.astype(np.float32))
 
 
-__all__ = ["IVocalSeparatorBackend", "SeparationOutputs", "MDX23HipBackend", "TrackSeparation", "items_per_chunk"]
+__all__ = ["IVocalSeparatorBackend", "SeparationOutputs", "MDX23HipBackend", "TrackSeparation", "TrackStemsPcm24", "items_per_chunk"]

@@ -97,6 +97,18 @@ class PackedTrack:
             x = np.asarray(audio)
             self.bytes, self.width = pcm_bytes_host(x.T if self.channels == 2 else x, subtype)
 
+    @classmethod
+    def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
+        """Wrap PCM_24 bytes that are ready (`ac_mdx_assemble_pcm24`): `3 * channels * n` of them, stereo frames interleaved
+        L, R - the layout the constructor produces."""
+        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, dtype=np.uint8).reshape(-1)
+        if channels not in (1, 2) or n < 0 or data.size != 3 * channels * n:
+            raise ValueError(f"expected {3 * channels * n} PCM_24 bytes for {n} frames of {channels} channel(s), got {data.size}")
+        track = cls.__new__(cls)
+        track.sample_rate, track.subtype, track.channels, track.n = int(sample_rate), "PCM_24", int(channels), int(n)
+        track.bytes, track.width = data, 3
+        return track
+
     def write(self, path: Path, start: int = 0, end: Optional[int] = None) -> Path:
         end = self.n if end is None else end
         start = max(0, min(int(start), self.n)); end = max(start, min(int(end), self.n))
