@@ -51,6 +51,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so hybrid ABI version mismatch")
     if lib.ac_export_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so export ABI version mismatch")
+    if lib.ac_asr_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so asr ABI version mismatch")
     _lib = lib
     return lib
 
@@ -149,10 +151,17 @@ EXPORT_SIGNATURES = {
     "ac_mdx_assemble_pcm24": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
 }
 
+# include/audiocut_hip_asr.h: the `vpbd_asr` mode's 16 kHz 16-bit copy of the vocal stem, exported by the same library and versioned
+# on its own
+ASR_SIGNATURES = {
+    "ac_asr_abi_version": (C.c_int, []),
+    "ac_resample_poly_pcm16": (C.c_int, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
+}
+
 
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
-                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items()):
+                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -452,6 +461,26 @@ class Context:
         out = torch.empty(n_out, dtype=torch.float32, device=self.device)
         _check(self.lib.ac_resample_poly(self._h, _ptr(x), n, up, down, _ptr(hd), hd.numel(), n_pre_remove, _ptr(out), n_out, _stream()))
         return out
+
+    def resample_poly_pcm16(self, x: torch.Tensor, up: int, down: int) -> np.ndarray:
+        """`resample_poly(x, up, down)` as finished 16-bit PCM on the host: int16 [ceil(n up / down)], every sample the float
+        `resample_poly` gives converted as `soundfile.write(subtype="PCM_16")` converts it (`pcm_bytes_host(.., "PCM_16")`), in one
+        launch (`ac_resample_poly_pcm16`) and one download of 2 bytes per sample; the floats never reach memory.  Equal rates
+        after reduction have nothing to resample: the stem is downloaded and converted on the host."""
+        import math
+        self._chk_f32(x)
+        g = math.gcd(int(up), int(down))
+        up, down = int(up) // g, int(down) // g
+        if up == down == 1:
+            from .utils.audio_export import pcm_bytes_host
+            return pcm_bytes_host(x.cpu().numpy(), "PCM_16")[0].view("<i2").copy()
+        n = x.numel()
+        n_out = n * up
+        n_out = n_out // down + bool(n_out % down)
+        hd, n_pre_remove = self._resample_filter_dev(up, down)
+        out = torch.empty(-(-n_out // 8) * 8, dtype=torch.int16, device=self.device)      # whole 16-byte groups (the last one zero padded)
+        _check(self.lib.ac_resample_poly_pcm16(self._h, _ptr(x), n, up, down, _ptr(hd), hd.numel(), n_pre_remove, _ptr(out), n_out, _stream()))
+        return out[:n_out].cpu().numpy()
 
     def resample_poly_segments(self, x: torch.Tensor, offsets: Sequence[int], lengths: Sequence[int], up: int, down: int, bucket: int = 0):
         """`resample_poly` of every segment x[offsets[s] : offsets[s] + lengths[s]] on its own, one launch.  Returns (out, out_off,

@@ -1,8 +1,7 @@
 """Normalised boundary features for VPBD scoring — mirrors the reference's
-`src/audio_cut/analysis/boundary_features.py:16-167`.  The lyrics timeline is always empty on the
-acoustic path (`vpbd_acoustic`; the ASR providers are out of scope): the four lyrics-derived
-features (`asr_gap`, `sentence_end`, `inside_word_penalty`, `singing_penalty`) are therefore constants 0 here and their
-evaluators are not built; the fields stay because the scorer's weight table names them."""
+`src/audio_cut/analysis/boundary_features.py:16-167`.  Six terms are acoustic (pause, beat and MDD affinity, breath, cached-RMS
+vocal risk, beat conflict); four read the lyrics timeline of mode `vpbd_asr` (`asr_gap`, `sentence_end`, `inside_word_penalty`,
+`singing_penalty`).  On the acoustic path the timeline is empty and those four are 0."""
 from __future__ import annotations
 
 from dataclasses import dataclass, field
@@ -10,22 +9,11 @@ from typing import Dict, Iterable, List
 
 import numpy as np
 
+from ..lyrics.models import LyricsTimeline       # the name stays importable from here (it was an empty stand-in before `vpbd_asr`)
+
 
 def _clamp01(v: float) -> float:
     return 0.0 if v < 0.0 else (1.0 if v > 1.0 else v)
-
-
-@dataclass
-class LyricsTimeline:
-    """The slice of `audio_cut.lyrics.models.LyricsTimeline` the acoustic path touches: an empty timeline."""
-
-    duration_s: float = 0.0
-    source: str = "none"
-    warnings: List[str] = field(default_factory=list)
-
-    def to_dict(self) -> Dict:
-        return {"duration_s": self.duration_s, "source": self.source, "words": [], "sentences": [], "vad_regions": [],
-                "warnings": list(self.warnings)}
 
 
 _FEATURE_NAMES = ("acoustic_pause", "asr_gap", "sentence_end", "inside_word_penalty", "singing_penalty", "beat_affinity",
@@ -61,6 +49,9 @@ class BoundaryFeatureExtractor:
     rms_series: Iterable[float] = field(default_factory=list)
     hop_s: float = 0.0
     high_confidence: float = 0.85
+    word_gap_norm_s: float = 1.5
+    sentence_tolerance_s: float = 0.25
+    word_edge_tolerance_ms: float = 60.0
     affinity_tolerance_s: float = 0.12
     vocal_risk_window_s: float = 0.08
 
@@ -73,9 +64,51 @@ class BoundaryFeatureExtractor:
 
     def extract(self, t: float, *, acoustic_pause: float = 0.0) -> BoundaryFeatures:
         return BoundaryFeatures(
-            acoustic_pause=acoustic_pause,            # asr_gap / sentence_end / inside_word / singing: no lyrics timeline on this path -> 0
+            acoustic_pause=acoustic_pause, asr_gap=self._asr_gap_score(t), sentence_end=self._sentence_end_score(t),
+            inside_word_penalty=self._inside_word_penalty(t), singing_penalty=self._singing_penalty(t),
             beat_affinity=self._affinity(t, self.beat_times), mdd_affinity=self._affinity(t, self.mdd_times),
             vocal_cut_risk=self._vocal_cut_risk(t), beat_conflict=self._beat_conflict(t))
+
+    # -- lyrics terms (reference `:86-126`); every loop is empty on an empty timeline -------------------------
+    def _confidence_weight(self, confidence) -> float:
+        if confidence is None:
+            return 0.5
+        return 1.0 if confidence >= self.high_confidence else 0.3
+
+    def _inside_word_penalty(self, t: float) -> float:
+        """cutting inside a word costs by the word's confidence, fading to 0 over `word_edge_tolerance_ms` towards its edges."""
+        for w in self.timeline.words:
+            if w.start_s < t < w.end_s:
+                base = self._confidence_weight(w.confidence)
+                tol = max(0.0, self.word_edge_tolerance_ms / 1000.0)
+                if tol <= 0.0:
+                    return base
+                edge = min(t - w.start_s, w.end_s - t)
+                return base * _clamp01(edge / tol) if edge < tol else base
+        return 0.0
+
+    def _singing_penalty(self, t: float) -> float:
+        for r in self.timeline.vad_regions:
+            if r.kind == "singing" and r.start_s < t < r.end_s:
+                return self._confidence_weight(r.confidence)
+        return 0.0
+
+    def _asr_gap_score(self, t: float) -> float:
+        words = self.timeline.words
+        for a, b in zip(words, words[1:]):
+            if a.end_s <= t <= b.start_s:
+                return _clamp01(max(0.0, b.start_s - a.end_s) / max(self.word_gap_norm_s, 1e-6))
+        return 0.0
+
+    def _sentence_end_score(self, t: float) -> float:
+        best = 0.0
+        for s in self.timeline.sentences:
+            d = abs(t - s.end_s)
+            if d > self.sentence_tolerance_s:
+                continue
+            conf = s.confidence if s.confidence is not None else 1.0
+            best = max(best, conf * (1.0 - (d / max(self.sentence_tolerance_s, 1e-6))))
+        return _clamp01(best)
 
     # -- acoustic terms ---------------------------------------------------------------------------------
     def _vocal_cut_risk(self, t: float) -> float:

@@ -2,7 +2,9 @@
 (`src/audio_cut/api.py:31-45`): load -> (resample) -> separate -> detect -> finalize -> boundary policy -> export ->
 SegmentManifest.
 
-Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, `librosa_onset`
+Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, `vpbd_asr` (the VPBD pool
+with a lyrics provider's timeline: `<name>_vocal_for_asr.wav`, the 16 kHz 16-bit copy of the vocal stem the provider is given, and a
+`lyrics` object per manifest segment), `librosa_onset`
 (bar-aligned smart segmentation: mix segments by default, vocal segments on request, no full stems) and
 `hybrid_mdd` (phrase-pause cuts snapped to beats in chorus bars: mix and vocal segments named `..._lib_D.D` where a segment ends on
 a beat, and the full vocal) and `vocal_separation` (the two stems and nothing else: `<name>_vocal_D.D.wav` and
@@ -12,8 +14,8 @@ is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; t
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
 `<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all PCM_24 packed on the GPU (`ac_pack_pcm24`).
-Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included; only the lyrics attachment to segments (ASR
-layer) is absent.  `separate_and_segment` returns the manifest like the reference's does.
+Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included, and the lyrics attachment to segments where an alignment
+ran.  `separate_and_segment` returns the manifest like the reference's does.
 
 `audio.channels` (1 or 2, validated like `config_manager.py:353-354`): with 2 the file is loaded as planar (2, N) float32
 (`load_audio_stereo`; a mono file goes to both channels), the network separates true L/R, and every exported WAV has two
@@ -32,6 +34,8 @@ import numpy as np
 
 from . import config as _config
 from .core.seamless_splitter import SeamlessSplitter
+from .lyrics.models import LyricsTimeline
+from .lyrics.segment_attach import attach_lyrics_to_segments
 
 
 def _read_wav(p: Path) -> tuple:
@@ -261,7 +265,8 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         if file_sr != sr:
             audio_dev = hip.resample_poly(hip.to_device(audio), sr, file_sr)     # e.g. 48 kHz -> 44.1 kHz = up 147 / down 160
             audio = audio_dev.cpu().numpy()
-    res = splitter.split_track(audio, mode=mode, audio_dev=audio_dev)
+    # `vpbd_asr`: the detector writes the 16 kHz ASR copy of the vocal stem next to the exports, named after the input
+    res = splitter.split_track(audio, mode=mode, audio_dev=audio_dev, input_path=str(in_path), output_dir=str(out_dir))
     if not res.get("success", True):                    # `split_audio_seamlessly`'s failure result (`:231-233`): nothing is written
         return {"success": False, "error": res.get("error"), "input_file": str(in_path), "mode": mode,
                 "timings": res.get("timings", {}), "processing_time": time.time() - t_start}
@@ -341,6 +346,8 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     if res.get("boundary_detection") is not None:
         out["boundary_detection"] = res["boundary_detection"]
         out["lyrics_alignment"] = res.get("lyrics_alignment")
+        if "lyrics_cut_protection_applied" in res:
+            out["lyrics_cut_protection_applied"] = bool(res["lyrics_cut_protection_applied"])
     out.update(res.get("gpu_meta", {}))
     return out
 
@@ -407,7 +414,9 @@ def _annotated_cuts(result: Mapping[str, Any]) -> list:
 
 
 def _manifest_segments(result: Mapping[str, Any], export_dir: Path) -> list:
-    """`_build_segments` (`api.py:266-304`) without the lyrics attachment (ASR layer, out of scope)."""
+    """`_build_segments` (`api.py:266-304`).  A result whose lyrics alignment ran (`lyrics_alignment.enabled`: mode `vpbd_asr`
+    with a provider switched on, fallbacks included) gets every segment's `lyrics` object - or None - from the timeline
+    (`lyrics/segment_attach.py`); every other result keeps its rows as they are."""
     times = list(result.get("cut_points_sec", []))
     durations = list(result.get("segment_durations", []))
     mix, voc = list(result.get("mix_segment_files", [])), list(result.get("vocal_segment_files", []))
@@ -425,7 +434,19 @@ def _manifest_segments(result: Mapping[str, Any], export_dir: Path) -> list:
         if i < len(debug) and debug[i]:
             row["debug"] = debug[i]
         rows.append(row)
-    return rows
+    timeline = _timeline_from_result(result)
+    return rows if timeline is None else attach_lyrics_to_segments(rows, timeline)
+
+
+def _timeline_from_result(result: Mapping[str, Any]):
+    """`_timeline_from_result` (`api.py:372-382`): the timeline the result carries, read leniently; None when no alignment ran."""
+    block = result.get("lyrics_alignment")
+    if not isinstance(block, Mapping) or not block.get("enabled") or not isinstance(block.get("timeline"), Mapping):
+        return None
+    try:
+        return LyricsTimeline.from_dict(dict(block["timeline"]), strict=False)
+    except Exception:
+        return None
 
 
 def _track_seconds(result: Mapping[str, Any], input_path: Path) -> Optional[float]:

@@ -14,6 +14,7 @@ names and signatures; their RMS(2048/441) passes run on the stems resident in HB
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
 import time
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -75,7 +76,8 @@ class SeamlessSplitter:
 
     # ------------------------------------------------------------------------------------------
     def split_track(self, original_audio: np.ndarray, mode: str = "v2.2_mdd", *, audio_dev=None, separation_gate=None,
-                    unet_stream=None, beat_analysis: bool = False, hybrid_density: Optional[str] = None) -> Dict:
+                    unet_stream=None, beat_analysis: bool = False, hybrid_density: Optional[str] = None, input_path: str = "",
+                    output_dir: str = "") -> Dict:
         """Steps 2-9 of SURVEY.md §3.1 on an in-memory mono float32 track at `sample_rate`.
         `separation_gate` (a lock shared by the workers of a `batch.TrackPipeline`) and `unet_stream` (the pipeline's one U-Net
         stream): with both, this track's separation is queued on that stream under the lock and the lock is released as soon as it is
@@ -90,7 +92,9 @@ class SeamlessSplitter:
         which reports its own bar analysis, and `hybrid_mdd`, which always reports the one its cuts were taken from.  Off, nothing
         is launched for it.
         `hybrid_density` ("low" / "medium" / "high") overrides `hybrid_mdd.beat_cut_density` for a `hybrid_mdd` track.
-        Mode `vocal_separation` separates and detects nothing: `_split_vocal_separation`."""
+        Mode `vocal_separation` separates and detects nothing: `_split_vocal_separation`.
+        `input_path` / `output_dir` reach the VPBD detector as `input_path` / `asr_output_dir` and name nothing else (`vpbd_asr`: where the 16 kHz ASR copy of the vocal stem is written and
+        what it is named after; empty: no file, the provider gets the samples only)."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
         sr = self.sample_rate
@@ -140,7 +144,8 @@ class SeamlessSplitter:
             # product configuration policy (out of scope): VPBD runs on the base configuration.
             vpbd = self.vpbd_detector.detect(mode=mode, vocal_track=vocal_track, original_audio=original_audio,
                                              pure_vocal_detector=self.pure_vocal_detector, feature_cache=cache,
-                                             vad_segments=sep.vad_segments, device_state=state)
+                                             vad_segments=sep.vad_segments, input_path=input_path, asr_output_dir=output_dir,
+                                             device_state=state)
             t_det = time.perf_counter() - t1
             cut_candidates = [(c.t, c.score) for c in vpbd.selected_candidates]
             rescue = [(c.t, c.score) for c in vpbd.planner_result.suppressed_candidates if float(c.score) > 0.0]
@@ -185,6 +190,13 @@ class SeamlessSplitter:
                                                    mix_dev=state.get("mix"), vocal_dev=state.get("vocal"))
         self._last_suppressed_cut_points = list(refine.suppressed_points or [])
         bounds = sorted(set(refine.sample_boundaries))
+        lyrics = vpbd.lyrics_alignment if is_vpbd and mode == "vpbd_asr" else None
+        if lyrics is not None:      # `:484-493`: a guard move from outside a word into one is undone
+            bounds, restored = self._restore_guard_points_outside_lyrics_words(
+                bounds, self._last_guard_adjustments_raw, self._collect_lyrics_word_intervals(lyrics),
+                sample_count=len(original_audio), min_gap_s=float(get_config("quality_control.min_split_gap", 1.0)))
+            if restored is not None:
+                self._last_guard_adjustments_raw = list(restored)
         if is_vpbd:         # `:494-499`: the planner block records where the guards moved each selected candidate
             from ..cutting.global_cut_planner import apply_guard_shift_metadata
             vpbd.boundary_detection["planner"] = dict(apply_guard_shift_metadata(vpbd.planner_result, self._last_guard_adjustments_raw).metadata)
@@ -198,8 +210,11 @@ class SeamlessSplitter:
             bounds = sorted(aug)
         t_fin = time.perf_counter() - t2
         t3 = time.perf_counter()
-        policy = self._apply_boundary_policy(bounds, vocal_track, len(original_audio), cache, vocal_dev=state.get("vocal"))
+        policy = self._apply_boundary_policy(bounds, vocal_track, len(original_audio), cache, vocal_dev=state.get("vocal"),
+                                             lyrics_alignment=lyrics)
         result.update(policy)
+        if mode == "vpbd_asr":
+            result["lyrics_cut_protection_applied"] = False         # `:658,767`: the reference reports the switch and never sets it
         result["timings_policy_s"] = time.perf_counter() - t3
         kept = list(self._last_guard_adjustments_raw)               # after the layout refiner's filter (`:602`)
         stats = self._guard_shift_stats(kept)
@@ -830,19 +845,22 @@ class SeamlessSplitter:
         return self._last_segment_spans, flags
 
     def _apply_boundary_policy(self, bounds: List[int], vocal_track: np.ndarray, n_samples: int,
-                               cache: Optional[TrackFeatureCache], *, vocal_dev=None) -> Dict:
-        """`:521-669` for the modes without lyrics alignment: classify -> layout refiner -> classify -> local valley ->
-        classify -> weak-tail merge -> sample-level split.  Returns the manifest-facing fields."""
+                               cache: Optional[TrackFeatureCache], *, vocal_dev=None, lyrics_alignment: Optional[Dict] = None) -> Dict:
+        """`:521-669`: classify -> layout refiner -> classify -> local valley -> classify -> weak-tail merge -> sample-level
+        split.  Returns the manifest-facing fields.  `lyrics_alignment` (mode `vpbd_asr` only): the layout refiner then reads the
+        vocal stem's RMS, the timeline's sentence / region boundaries and word intervals, and the local valley search keeps out of
+        the words (`:547-551,575-584,624-628`)."""
         from ..cutting.segment_layout_refiner import Segment as LayoutSegment, derive_layout_config, refine_layout
         sr = self.sample_rate
         cuts = sorted(set(int(c) for c in bounds))
         self._segment_measure_cache = {}
         try:
-            return self._boundary_policy_steps(cuts, vocal_track, n_samples, cache, vocal_dev)
+            return self._boundary_policy_steps(cuts, vocal_track, n_samples, cache, vocal_dev, lyrics_alignment)
         finally:
             self._segment_measure_cache = None
 
-    def _boundary_policy_steps(self, cuts: List[int], vocal_track: np.ndarray, n_samples: int, cache, vocal_dev) -> Dict:
+    def _boundary_policy_steps(self, cuts: List[int], vocal_track: np.ndarray, n_samples: int, cache, vocal_dev,
+                               lyrics_alignment: Optional[Dict] = None) -> Dict:
         from ..cutting.segment_layout_refiner import Segment as LayoutSegment, derive_layout_config, refine_layout
         sr = self.sample_rate
         flags = self._classify_segments_vocal_presence(vocal_track, cuts, vocal_dev=vocal_dev)
@@ -855,13 +873,18 @@ class SeamlessSplitter:
             raw.setdefault("soft_max_s", float(smax))
         raw.setdefault("min_gap_s", float(get_config("quality_control.min_split_gap", 1.0)))
         raw.setdefault("beat_snap_ms", float(get_config("segment_layout.beat_snap_ms", 0.0) or 0.0))
+        asr = lyrics_alignment is not None
+        if asr:
+            cache = self._build_vocal_layout_feature_cache(cache, vocal_track, vocal_dev=vocal_dev)
         lcfg = derive_layout_config(raw, cache, sample_rate=sr)
         applied = False
         if lcfg.enable and len(cuts) >= 2:
             edges = [c / float(sr) for c in cuts]
             res = refine_layout([LayoutSegment(edges[i], edges[i + 1], "human" if flags[i] else "music") for i in range(len(edges) - 1)],
                                 self._last_guard_adjustments_raw, config=lcfg, sample_rate=sr,
-                                suppressed_cut_points=self._last_suppressed_cut_points, features=cache)
+                                suppressed_cut_points=self._last_suppressed_cut_points, features=cache,
+                                asr_boundary_times=self._collect_lyrics_boundary_times(lyrics_alignment) if asr else None,
+                                asr_word_intervals=self._collect_lyrics_word_intervals(lyrics_alignment) if asr else None)
             if res.segments:
                 times = [res.segments[0].start] + [sg.end for sg in res.segments]
                 upd = [max(0, min(int(round(t * sr)), n_samples)) for t in times]
@@ -877,6 +900,7 @@ class SeamlessSplitter:
         local = get_config("quality_control.local_boundary_refine", {}) or {}
         if local.get("enable") and len(cuts) >= 2:
             ref = self._refine_boundaries_local_valley(cuts, vocal_track, local, min_gap_s=float(get_config("quality_control.min_split_gap", 1.0)),
+                                                       protected_intervals_s=self._collect_lyrics_word_intervals(lyrics_alignment) if asr else None,
                                                        vocal_dev=vocal_dev)
             if list(ref) != cuts:
                 cuts = list(ref); applied = True
@@ -893,6 +917,106 @@ class SeamlessSplitter:
                 "segment_spans": spans, "segment_durations": [(hi - lo) / float(sr) for lo, hi in spans],
                 "segment_layout_applied": bool(applied),
                 "suppressed_cut_points_sec": [float(c.t) for c in self._last_suppressed_cut_points]}
+
+    # ---- mode `vpbd_asr`: what the timeline feeds into the boundary policy (reference `:896-938,1880-2004`) ----------------
+    def _build_vocal_layout_feature_cache(self, cache: Optional[TrackFeatureCache], vocal_track: Optional[np.ndarray], *, vocal_dev=None):
+        """A copy of the cache whose RMS series follows the VOCAL stem (the layout refiner's valley rescue then looks for quiet
+        singing, not a quiet mix): `librosa.feature.rms` of the stem at `max(2 hop, 0.1 s)` per frame and the cache's hop, padded with
+        its last value or cropped to the cache's frame count.  One `ac_frame_rms` launch on the resident stem."""
+        if cache is None or vocal_track is None:
+            return cache
+        sr, hop = int(getattr(cache, "sr", 0) or 0), int(getattr(cache, "hop_length", 0) or 0)
+        if sr <= 0 or hop <= 0 or np.size(vocal_track) == 0:
+            return cache
+        frame = max(2 * hop, int(round(sr * 0.1)))
+        try:            # as in the reference (`:936-938`): a stem shorter than one frame or a frame beyond the kernel's limit keeps the mix cache
+            rms = self._context().frame_rms(self._vocal_on_device(vocal_track, vocal_dev), frame, hop).cpu().numpy().astype(np.float32, copy=False)
+        except Exception as exc:
+            logger.debug("[Layout] vocal RMS feature cache not built: %s", exc)
+            return cache
+        if rms.size == 0:
+            return cache
+        want = int(cache.frame_count())
+        if want > 0 and rms.size != want:
+            rms = np.pad(rms, (0, want - rms.size), constant_values=float(rms[-1])) if rms.size < want else rms[:want]
+        return dataclasses.replace(cache, rms_series=rms, rms_max=float(np.max(rms)))
+
+    def _restore_guard_points_outside_lyrics_words(self, final_cut_points: List[int], adjustments: Sequence, word_intervals, *,
+                                                   sample_count: int, min_gap_s: float):
+        """-> (boundaries, adjustments or None when nothing changed).  A guard may push a cut that lay between two words into
+        one; such a cut goes back to its raw time when that keeps `min_gap_s` to both neighbours and is not an end of the track.
+        The restored cut's adjustment is rewritten as "not moved"."""
+        if not final_cut_points or not adjustments or not word_intervals:
+            return list(final_cut_points), None
+        sr = float(self.sample_rate)
+        min_gap = max(0, int(round(float(min_gap_s) * sr)))
+        words = sorted(word_intervals)
+
+        def inside(t: float) -> bool:
+            for a, b in words:
+                if a < t < b:
+                    return True
+                if a >= t:
+                    break
+            return False
+
+        to_sample = lambda t: max(0, min(int(round(t * sr)), sample_count))
+        points = sorted({max(0, min(int(p), sample_count)) for p in final_cut_points})
+        restored = set()
+        for adj in adjustments:
+            raw_t, final_t = float(adj.raw_time), float(adj.final_time)
+            if not inside(final_t) or inside(raw_t):
+                continue
+            raw, final = to_sample(raw_t), to_sample(final_t)
+            if final not in points or raw in (0, sample_count):
+                continue
+            trial = sorted(raw if p == final else p for p in points)
+            i = trial.index(raw)
+            if (i > 0 and trial[i] - trial[i - 1] < min_gap) or (i < len(trial) - 1 and trial[i + 1] - trial[i] < min_gap):
+                continue
+            points = trial
+            restored.add(raw_t)
+        if not restored:
+            return list(final_cut_points), None
+        from ..cutting.refine import CutAdjustment
+        return points, [CutAdjustment(raw_time=a.raw_time, guard_time=a.raw_time, final_time=a.raw_time, score=a.score,
+                                      guard_shift_ms=0.0, final_shift_ms=0.0) if float(a.raw_time) in restored else a
+                        for a in adjustments]
+
+    @staticmethod
+    def _timeline_rows(lyrics_alignment, key: str):
+        timeline = lyrics_alignment.get("timeline") if isinstance(lyrics_alignment, dict) else None
+        rows = (timeline.get(key, []) or []) if isinstance(timeline, dict) else []
+        return [r for r in rows if isinstance(r, dict)]
+
+    @staticmethod
+    def _collect_lyrics_word_intervals(lyrics_alignment: Optional[Dict]) -> List[Tuple[float, float]]:
+        """(start, end) of every well-formed word of `lyrics_alignment["timeline"]`, sorted, duplicates dropped."""
+        out = set()
+        for w in SeamlessSplitter._timeline_rows(lyrics_alignment, "words"):
+            try:
+                a, b = float(w.get("start_s")), float(w.get("end_s"))
+            except (TypeError, ValueError):
+                continue
+            if b > a:
+                out.add((a, b))
+        return sorted(out)
+
+    @staticmethod
+    def _collect_lyrics_boundary_times(lyrics_alignment: Optional[Dict]) -> List[float]:
+        """every sentence end and every edge of a VAD region, > 0, sorted, duplicates dropped: soft priors of the layout refiner."""
+        values = [s.get("end_s") for s in SeamlessSplitter._timeline_rows(lyrics_alignment, "sentences")]
+        for r in SeamlessSplitter._timeline_rows(lyrics_alignment, "vad_regions"):
+            values += [r.get("start_s"), r.get("end_s")]
+        out = set()
+        for v in values:
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                continue
+            if v > 0.0:
+                out.add(v)
+        return sorted(out)
 
     def _rms2048_db(self, wave: np.ndarray, dev=None) -> np.ndarray:
         hip = self._context()

@@ -1,13 +1,15 @@
-"""VPBD unified candidate pool (mode `vpbd_acoustic`) — mirrors the acoustic path of the reference's
-`src/vocal_smart_splitter/core/vocal_phrase_boundary_detector.py:49-385`:
-acoustic pauses from `PureVocalPauseDetector` (HIP kernels) + weak beat candidates in high-energy bars +
-+-120 ms fusion + feature scoring (MDD valleys, cached-RMS vocal risk, beat affinity/conflict) + the
-global DP planner.  Host logic over <= a few hundred candidates; the heavy lifting (stems, caches, pauses)
-is already in HBM-resident kernels upstream.
+"""VPBD unified candidate pool (modes `vpbd_acoustic` and `vpbd_asr`) — mirrors the reference's
+`src/vocal_smart_splitter/core/vocal_phrase_boundary_detector.py:49-411`:
+acoustic pauses from `PureVocalPauseDetector` (HIP kernels) + weak beat candidates in high-energy bars + the lyrics candidates of
+a provider's timeline + +-120 ms fusion + feature scoring (MDD valleys, cached-RMS vocal risk, beat affinity/conflict, word gaps,
+sentence ends, inside-word and singing penalties) + the global DP planner.  Host logic over <= a few hundred candidates; the
+heavy lifting (stems, caches, pauses) is already in HBM-resident kernels upstream.
 
-`vpbd_asr` resolves to `vpbd_acoustic` with `fallback_reason="lyrics_alignment_disabled"`, exactly what the
-reference does when `lyrics_alignment.enabled` is false (`:78-80`, the shipped default `unified.yaml:28-29`);
-the ASR providers themselves are out of scope.
+`vpbd_asr` with `lyrics_alignment.enabled` false (the shipped default, `unified.yaml:28-29`) resolves to `vpbd_acoustic` with
+`fallback_reason="lyrics_alignment_disabled"` (`:78-80`).  Switched on, the mode asks a `LyricsProvider` (`lyrics/providers.py`)
+for the track's timeline; what it hands the provider is the vocal stem as 16 kHz 16-bit PCM, made on the GPU in one kernel from
+the resident stem (`ac_resample_poly_pcm16`, reference `:388-411`).  The ASR engines themselves are external: a host application
+sets its own provider as `VocalPhraseBoundaryDetector.lyrics_provider`.
 """
 from __future__ import annotations
 
@@ -18,6 +20,9 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 
 from ..analysis.boundary_features import BoundaryFeatureExtractor, LyricsTimeline
+from ..exceptions import LyricsAlignmentUnavailable
+from ..lyrics.candidates import LyricsBoundaryCandidateGenerator
+from ..lyrics.providers import LyricsProvider, LyricsProviderRequest, build_lyrics_provider
 from ..config import get_config
 from ..cutting.beat_candidates import generate_beat_candidates
 from ..cutting.cut_candidate import CandidateSource, CutCandidate, adapt_legacy_acoustic_candidates
@@ -52,12 +57,19 @@ def _planner_config() -> GlobalCutPlannerConfig:
 
 
 class VocalPhraseBoundaryDetector:
+    ASR_SAMPLE_RATE = 16000
+
     def __init__(self, sample_rate: int = 44100) -> None:
         self.sample_rate = sample_rate
+        self.lyrics_provider: Optional[LyricsProvider] = None      # a host application's own ASR; None: `build_lyrics_provider`
 
     def detect(self, *, mode: str, vocal_track: np.ndarray, original_audio: np.ndarray, pure_vocal_detector: Any,
                feature_cache: Optional[Any], vad_segments: Optional[List[Dict[str, float]]], input_path: str = "",
-               output_dir: str = "", device_state: Optional[Dict[str, Any]] = None) -> VPBDDetectionResult:
+               output_dir: str = "", device_state: Optional[Dict[str, Any]] = None,
+               asr_output_dir: Optional[str] = None) -> VPBDDetectionResult:
+        """`output_dir`: where the candidate debug JSON (`vpbd.candidate_debug_json`) and the ASR copy go, as in the reference.
+        `asr_output_dir`, when given, is where the ASR copy goes instead: `split_track` passes the export directory through it
+        alone, so that no mode starts writing the debug JSON into a user's export directory."""
         sr = self.sample_rate
         duration_s = len(original_audio) / float(sr) if sr > 0 else 0.0
         actual_mode, fallback_reason = mode, None
@@ -70,38 +82,81 @@ class VocalPhraseBoundaryDetector:
         lyrics_cfg = _section("lyrics_alignment")
         strict = bool(lyrics_cfg.get("strict", False))
         lyrics_enabled = bool(lyrics_cfg.get("enabled", False)) and mode == "vpbd_asr"
-        if mode == "vpbd_asr":
-            if lyrics_enabled:
-                raise NotImplementedError("lyrics/ASR providers are outside the separate+detect hot path (SURVEY.md §2 #16)")
-            actual_mode, fallback_reason = "vpbd_acoustic", "lyrics_alignment_disabled"
-
+        provider_name = str(lyrics_cfg.get("provider", "disabled"))
+        lyrics: List[CutCandidate] = []
         state = device_state or {}
+        if mode == "vpbd_asr" and not lyrics_enabled:
+            actual_mode, fallback_reason = "vpbd_acoustic", "lyrics_alignment_disabled"
+        elif mode == "vpbd_asr":                 # reference `:83-116`
+            provider = self.lyrics_provider
+            if provider is None:
+                provider = build_lyrics_provider(dict(lyrics_cfg, fire_red=_section("fire_red")))
+            provider_name = provider.name
+            try:
+                if provider.name == "null":
+                    raise LyricsAlignmentUnavailable(str(getattr(provider, "reason", "lyrics alignment unavailable")))
+                asr_path, pcm16 = self._asr_vocal_copy(state, input_path, output_dir if asr_output_dir is None else asr_output_dir)
+                timeline = provider.align(LyricsProviderRequest(
+                    vocal_path=asr_path, duration_s=duration_s, sample_rate=self.ASR_SAMPLE_RATE, strict=strict,
+                    meta={} if pcm16 is None else {"pcm16": pcm16}))
+                lyrics = LyricsBoundaryCandidateGenerator().generate(timeline)
+            except LyricsAlignmentUnavailable:
+                if strict:
+                    raise
+                actual_mode, fallback_reason = "vpbd_acoustic", "lyrics_alignment_unavailable"
+            except Exception as exc:
+                if strict:
+                    raise
+                actual_mode, fallback_reason = "vpbd_acoustic", str(exc)
+
         acoustic = self._build_acoustic_candidates(vocal_track=vocal_track, original_audio=original_audio,
                                                    pure_vocal_detector=pure_vocal_detector, feature_cache=feature_cache,
                                                    vad_segments=vad_segments, enable_mdd=True, include_breath_candidates=unified,
                                                    device_state=state)
         beats = self._build_beat_candidates(vocal_track=vocal_track, feature_cache=feature_cache, duration_s=duration_s,
                                             device_state=state) if unified else []
-        merged = self._merge_candidate_pool(acoustic, [], beats)
+        pooled = lyrics if unified else []        # the legacy pool keeps the timeline for scoring only
+        merged = self._merge_candidate_pool(acoustic, pooled, beats)
         scored = self._score_candidates(candidates=merged, timeline=timeline, feature_cache=feature_cache)
         debug_path: Optional[str] = None
         if bool(vpbd_cfg.get("candidate_debug_json", False)) and output_dir:
             debug_path = str(Path(output_dir) / "vpbd_candidate_debug.json")
             write_candidate_debug_json(scored, debug_path)
         plan = GlobalCutPlanner(_planner_config()).plan(scored, duration_s=duration_s)
-        lyrics_meta = {"enabled": lyrics_enabled, "provider": str(lyrics_cfg.get("provider", "disabled")), "strict": strict,
-                       "fallback_reason": fallback_reason, "word_count": 0, "sentence_count": 0, "vad_region_count": 0,
-                       "warnings": [], "timeline": timeline.to_dict()}
+        lyrics_meta = {"enabled": lyrics_enabled, "provider": provider_name, "strict": strict,
+                       "fallback_reason": fallback_reason, "word_count": len(timeline.words), "sentence_count": len(timeline.sentences),
+                       "vad_region_count": len(timeline.vad_regions), "warnings": list(timeline.warnings), "timeline": timeline.to_dict()}
         boundary_meta = {
             "mode": mode, "actual_mode": actual_mode, "candidate_pool": pool, "candidate_debug_path": debug_path,
-            "candidate_counts": {"acoustic": len(acoustic), "lyrics": 0, "lyrics_pooled": 0, "beat": len(beats),
+            "candidate_counts": {"acoustic": len(acoustic), "lyrics": len(lyrics), "lyrics_pooled": len(pooled), "beat": len(beats),
                                  "merged": len(merged), "total": len(scored), "selected": len(plan.selected_candidates),
-                                 "suppressed": len(plan.suppressed_candidates), "lyrics_soft_prior": 0},
+                                 "suppressed": len(plan.suppressed_candidates), "lyrics_soft_prior": len(lyrics)},
             "planner": dict(plan.metadata),
             "selected": [c.to_dict() for c in plan.selected_candidates],
             "suppressed": [c.to_dict() for c in plan.suppressed_candidates],
         }
         return VPBDDetectionResult(list(plan.selected_candidates), plan, boundary_meta, lyrics_meta)
+
+    # -- the ASR copy (reference `_write_asr_vocal_copy`, `:388-411`) --------------------------------------------
+    def _asr_vocal_copy(self, state: Dict[str, Any], input_path: str, output_dir: str):
+        """-> (path or None, int16 array or None).  The resident vocal stem as mono 16 kHz 16-bit PCM, in one kernel and one
+        download (`Context.resample_poly_pcm16`: the resampler's floats go through the WAV writer's conversion without ever
+        being stored; its saturation is the reference's `np.clip(-1, 1)`).  With an `output_dir` it is also written as
+        `<stem of input_path>_vocal_for_asr.wav`.  Without device state (host-only callers) no copy is made."""
+        hip, vocal = state.get("hip"), state.get("vocal")
+        if hip is None or vocal is None:
+            return None, None
+        pcm16 = hip.resample_poly_pcm16(vocal, self.ASR_SAMPLE_RATE, self.sample_rate)
+        if not output_dir:
+            return None, pcm16
+        from ..utils.audio_export import wav_header
+        target = Path(output_dir)
+        target.mkdir(parents=True, exist_ok=True)
+        path = target / f"{Path(input_path).stem}_vocal_for_asr.wav"
+        with open(path, "wb") as fh:
+            fh.write(wav_header(int(pcm16.size), self.ASR_SAMPLE_RATE, 1, 2))
+            fh.write(np.ascontiguousarray(pcm16, dtype="<i2").tobytes())
+        return path, pcm16
 
     # -- pool members ---------------------------------------------------------------------------------------
     def _build_acoustic_candidates(self, *, vocal_track, original_audio, pure_vocal_detector, feature_cache, vad_segments,
@@ -177,7 +232,7 @@ class VocalPhraseBoundaryDetector:
         hop_s = float(getattr(feature_cache, "hop_s", 0.0) or 0.0) if feature_cache is not None else 0.0
         extractor = BoundaryFeatureExtractor(
             timeline=timeline, beat_times=beat_times, mdd_times=self._mdd_valley_times(feature_cache), rms_series=rms_series,
-            hop_s=hop_s)
+            hop_s=hop_s, word_edge_tolerance_ms=float(_section("phrase_boundary").get("word_edge_tolerance_ms", 60.0)))
         scorer = PhraseBoundaryScorer.from_config(_section("phrase_boundary"))
         out: List[CutCandidate] = []
         for c in candidates:

@@ -230,3 +230,12 @@ __device__ inline int pcm24(float v) {
     if (!(s == s)) return 0;                             // NaN: lrintf is undefined there; silence
     return ((int)rintf(s)) >> 8;                         // lrintf (half to even), then the three high bytes
 }
+
+// ---- float32 -> 16-bit PCM word (ac_resample_poly_pcm16): libsndfile pcm.c f2les_clip_array, the same conversion two bytes wide ---
+__device__ inline int pcm16(float v) {
+    const float s = v * 2147483648.0f;
+    if (s >= 2147483647.0f) return 32767;
+    if (s <= -2147483648.0f) return -32768;
+    if (!(s == s)) return 0;
+    return ((int)rintf(s)) >> 16;                        // lrintf (half to even), then the two high bytes
+}
