@@ -53,6 +53,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so export ABI version mismatch")
     if lib.ac_asr_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so asr ABI version mismatch")
+    if lib.ac_profile_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so profile ABI version mismatch")
     _lib = lib
     return lib
 
@@ -158,10 +160,29 @@ ASR_SIGNATURES = {
     "ac_resample_poly_pcm16": (C.c_int, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
 }
 
+# include/audiocut_hip_profile.h: AutoProfile's vocal coverage (peak and count over the resident stem), exported by the same library
+# and versioned on its own
+PROFILE_SIGNATURES = {
+    "ac_profile_abi_version": (C.c_int, []),
+    "ac_abs_peak_coverage": (C.c_int, [_P, _P, _I64, C.c_double, C.c_double, _P, _P, _P, _P]),
+}
+# 4 * AC_PROFILE_BLOCK * AC_PROFILE_MAX_BLOCKS: the samples one step of the largest grid of ac_abs_peak_coverage covers (from
+# twice this many on, every thread of either sweep goes round its loop at least twice)
+PROFILE_GRID_SAMPLES = 4 * 256 * 2048
+
+
+def coverage_from(peak: float, count: int, n: int) -> float:
+    """The reference's vocal coverage (`seamless_splitter.py:884-891`) from the kernel's exact results: 0.0 for an empty or silent
+    stem (`peak <= 1e-9`), else count / n in float64 - what `float(np.mean(bool_array))` gives, a sum of 0/1 being exact -
+    clamped to [0, 1]."""
+    if int(n) == 0 or float(peak) <= 1e-9:
+        return 0.0
+    return max(0.0, min(1.0, int(count) / int(n)))
+
 
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
-                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items()):
+                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -676,6 +697,21 @@ class Context:
                                              base + 8 * nb if k else None, base + 8 * (nb + k) if k else None, _stream()))
         host = out.cpu().numpy()
         return host[:nb].copy(), host[nb:nb + k].copy(), host[nb + k:].view(np.int64).copy()
+
+    # -- AutoProfile's vocal coverage (include/audiocut_hip_profile.h) -----------------------------------
+    def vocal_coverage(self, x_dev: torch.Tensor, rel: float = 0.03, abs_floor: float = 1e-5) -> Tuple[float, np.float32, int]:
+        """(peak, thr, count) of the resident float32 signal: peak = max |x|, thr = float32(max(peak * rel, abs_floor)), count = the
+        number of samples with |x| >= thr.  Three launches queued back to back, one 16-byte download; `coverage_from` turns the
+        result into the reference's ratio.  `x_dev` may be a slice (any 4-byte aligned address)."""
+        self._chk_f32(x_dev)
+        n = int(x_dev.numel())
+        out = torch.empty(2, dtype=torch.int64, device=self.device)         # peak (f32) | thr (f32) | count (i64)
+        base = out.data_ptr()
+        _check(self.lib.ac_abs_peak_coverage(self._h, _ptr(x_dev) if n else None, n, float(rel), float(abs_floor), base, base + 4,
+                                             base + 8, _stream()))
+        host = out.cpu().numpy()
+        f = host[:1].view(np.float32)
+        return float(f[0]), np.float32(f[1]), int(host[1])
 
     def local_valley(self, x: torch.Tensor, centers: np.ndarray, radius: int, win: int):
         """(orig_db, min_db, min_idx) per boundary, host arrays (see ac_local_valley)."""

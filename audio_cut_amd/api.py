@@ -2,6 +2,11 @@
 (`src/audio_cut/api.py:31-45`): load -> (resample) -> separate -> detect -> finalize -> boundary policy -> export ->
 SegmentManifest.
 
+`segments` (`few` / `medium` / `many`, `"MIN-MAX"` or `(min_s, max_s)`) and `alignment` (`lyric` / `lyric_lean` / `balanced` /
+`beat_lean` / `beat` or 0..1) are the smart-cut intent: given either, the default mode is `vpbd_asr`, the lyrics provider is `auto`,
+and the splitter derives planner, scorer, detector and layout settings from them and from the track's estimated style
+(AutoProfile, `config/auto_profile.py`); the manifest carries `intent` and `auto_profile` (`smart_cut`).
+
 Modes `v2.2_mdd` (default when no intent arguments are given, `api.py:74-75`), `v2.1`, `vpbd_acoustic`, `vpbd_asr` (the VPBD pool
 with a lyrics provider's timeline: `<name>_vocal_for_asr.wav`, the 16 kHz 16-bit copy of the vocal stem the provider is given, and a
 `lyrics` object per manifest segment), `librosa_onset`
@@ -33,6 +38,7 @@ from typing import Any, Dict, Mapping, Optional, Sequence
 import numpy as np
 
 from . import config as _config
+from .config.auto_profile import resolve_smart_cut_intent
 from .core.seamless_splitter import SeamlessSplitter
 from .lyrics.models import LyricsTimeline
 from .lyrics.segment_attach import attach_lyrics_to_segments
@@ -195,15 +201,13 @@ def separate_and_segment(*, input_uri: str, export_dir: str, mode: Optional[str]
                          runtime_overrides: Optional[Dict[str, Any]] = None) -> Dict:
     """Returns the SegmentManifest dict (`api.py:115-131`); with `export_manifest` it is also written under `export_dir`
     and carries `manifest_path`.  The splitter's own result (`split_audio_seamlessly`'s dict) is `last_result()`."""
-    if segments is not None or alignment is not None:
-        raise NotImplementedError("intent routing (segments/alignment) belongs to the product layers outside the "
-                                  "separate+detect hot path (SURVEY.md §2 #13,#15)")
+    has_intent = segments is not None or alignment is not None
     in_path = Path(input_uri).expanduser().resolve()
     if not in_path.exists():
         raise FileNotFoundError(f"input audio not found: {in_path}")
     out_dir = Path(export_dir).expanduser().resolve()
     out_dir.mkdir(parents=True, exist_ok=True)
-    resolved_mode = mode or "v2.2_mdd"
+    resolved_mode = mode or ("vpbd_asr" if has_intent else "v2.2_mdd")     # `api.py:74-75`: an explicit mode wins
     saved = _config.snapshot()
     try:
         overrides: Dict[str, Any] = {}
@@ -216,12 +220,23 @@ def separate_and_segment(*, input_uri: str, export_dir: str, mode: Optional[str]
             overrides["segment_layout.enable"] = bool(lay.pop("enable", True))
             for k, v in lay.items():
                 overrides[f"segment_layout.{k}"] = v
+        if has_intent:                                                   # `_build_intent_runtime_overrides` (`api.py:134-144`)
+            overrides.update({"lyrics_alignment.enabled": True, "lyrics_alignment.provider": "auto", "lyrics_alignment.strict": False})
+            if segments is not None:
+                overrides["smart_cut.segments"] = segments
+            if alignment is not None:
+                overrides["smart_cut.alignment"] = alignment
         overrides.update(dict(runtime_overrides or {}))                 # explicit dotted overrides are applied last (`:168-175`)
-        _config.set_runtime_config(overrides)
+        # written like the reference writes them, straight into the tree (`:147-175`): they override, and the smart-cut layer does
+        # not read them as keys the caller set on purpose (`config.get_runtime_override_keys`)
+        _config.set_runtime_config(overrides, explicit=False)
+        intent_echo = resolve_smart_cut_intent(_config.get_config("smart_cut", {}) or {}) if has_intent else None   # `:97-100`
         layout_cfg = dict(_config.get_config("segment_layout", {}) or {})
         sr = int(_config.get_config("audio.sample_rate", 44100))
         channels = _check_channels(_config.get_config("audio.channels", 1))
         result = _split_and_export(in_path, out_dir, resolved_mode, export_types, sr, device, channels)
+        if intent_echo is not None:
+            result.setdefault("intent", intent_echo)                    # the splitter's own record, with `applied_overrides`, stays
     finally:
         _config.restore(saved)
     global _LAST_RESULT
@@ -348,6 +363,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         out["lyrics_alignment"] = res.get("lyrics_alignment")
         if "lyrics_cut_protection_applied" in res:
             out["lyrics_cut_protection_applied"] = bool(res["lyrics_cut_protection_applied"])
+    for key in ("auto_profile", "intent"):              # a smart-cut run (`seamless_splitter.py:761-765`)
+        if res.get(key) is not None:
+            out[key] = res[key]
     out.update(res.get("gpu_meta", {}))
     return out
 

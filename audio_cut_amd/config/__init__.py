@@ -4,15 +4,20 @@ restricted to the keys SURVEY.md Appendix A lists for the separate+detect path.
 
 `get_config(path, default)` has the reference's semantics: dotted lookup, `default` when the key is absent
 (several call sites rely on their literal default because the YAML omits the key).  `set_runtime_config`
-/ `reset_runtime_config` mirror `config_manager.py:497-509` (dotted-key overrides layered on top).
+/ `reset_runtime_config` mirror `config_manager.py:497-509` (dotted-key overrides layered on top), and
+`get_runtime_override_keys` (`:512-515`) names the keys a caller set through it: the smart-cut intent layer
+(`config/auto_profile.py`) treats those as stated on purpose even where the value equals the default.
 """
 from __future__ import annotations
 
 import copy
 import os
-from typing import Any, Dict
+from typing import Any, Dict, Set
 
 DEFAULTS: Dict[str, Any] = {
+    # the v2.8 intent surface (`unified.yaml:8-14`); read by `SeamlessSplitter._apply_smart_cut_runtime` alone
+    "smart_cut": {"segments": "medium", "alignment": "balanced", "profile": "auto", "cut_style": "natural",
+                  "target_duration_s": [5.0, 12.0], "lyrics": "auto"},
     "audio": {"sample_rate": 44100, "channels": 1},
     "gpu_pipeline": {
         "enable": True, "prefer_device": "cuda", "strict_gpu": False,
@@ -79,6 +84,13 @@ DEFAULTS: Dict[str, Any] = {
         "word_edge_tolerance_ms": 60.0,
         "weights": {"acoustic_pause": 0.35, "asr_gap": 0.2, "sentence_end": 0.15, "beat_affinity": 0.08, "mdd_affinity": 0.1,
                     "breath": 0.12, "inside_word_penalty": 0.8, "singing_penalty": 0.5},
+        # the two ends of the alignment axis (`expert.yaml:194-212`); `derive_alignment_overrides` blends the style's weights towards one
+        "alignment_poles": {
+            "lyric": {"acoustic_pause": 0.38, "asr_gap": 0.26, "sentence_end": 0.22, "beat_affinity": 0.02, "mdd_affinity": 0.06,
+                      "breath": 0.10, "inside_word_penalty": 0.85, "singing_penalty": 0.50},
+            "beat": {"acoustic_pause": 0.22, "asr_gap": 0.10, "sentence_end": 0.08, "beat_affinity": 0.32, "mdd_affinity": 0.12,
+                     "breath": 0.10, "inside_word_penalty": 0.80, "singing_penalty": 0.50},
+        },
     },
     "global_planner": {
         "enable": True, "hard_min_s": 2.0, "hard_max_s": 18.0, "target_min_s": 5.0, "target_max_s": 12.0,
@@ -108,6 +120,7 @@ DEFAULTS: Dict[str, Any] = {
 }
 
 _runtime: Dict[str, Any] = {}
+_explicit: Set[str] = set()       # the keys of `_runtime` that went in through `set_runtime_config(..., explicit=True)`
 _MISSING = object()
 
 
@@ -222,21 +235,46 @@ def get_hybrid_mdd_config(density_override: Any = None) -> Dict[str, Any]:
     }
 
 
-def set_runtime_config(overrides: Dict[str, Any]) -> None:
-    """Dotted-key overrides (reference: config_manager.py:497-509).  A key written again moves to the end (last write wins)."""
+def set_runtime_config(overrides: Dict[str, Any], *, explicit: bool = True) -> None:
+    """Dotted-key overrides (reference: config_manager.py:497-509).  A key written again moves to the end (last write wins).
+    `explicit` (the default, and what the reference's function does): the keys are reported by `get_runtime_override_keys`.
+    `explicit=False` is the reference API's own way in - it writes device, layout, intent and `runtime_overrides` straight into
+    the tree (`api.py:147-175`), so they override without counting as stated by the caller; a key the caller had marked before
+    stays marked, as it does there."""
     for k, v in (overrides or {}).items():
         _runtime.pop(str(k), None)
         _runtime[str(k)] = v
+        if explicit:
+            _explicit.add(str(k))
+
+
+def get_runtime_override_keys() -> Set[str]:
+    """The dotted keys set through `set_runtime_config` and still in force (`config_manager.py:512-515`), as a copy."""
+    return set(_explicit)
 
 
 def reset_runtime_config() -> None:
     _runtime.clear()
+    _explicit.clear()
+
+
+class _Snapshot(dict):
+    """`snapshot()`'s value: the override map, as before, and with it the explicit-key set of that moment."""
+    explicit: frozenset = frozenset()
 
 
 def snapshot() -> Dict[str, Any]:
-    return dict(_runtime)
+    saved = _Snapshot(_runtime)
+    saved.explicit = frozenset(_explicit)
+    return saved
 
 
 def restore(saved: Dict[str, Any]) -> None:
+    """Back to `saved`: the overrides, and the explicit keys `snapshot()` recorded with them (a plain dict: those of its keys that
+    were explicit until now)."""
+    marks = getattr(saved, "explicit", None)
+    keep = set(marks) if marks is not None else {k for k in _explicit if k in saved}
     _runtime.clear()
     _runtime.update(saved)
+    _explicit.clear()
+    _explicit.update(k for k in keep if k in _runtime)

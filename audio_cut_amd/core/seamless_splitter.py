@@ -25,7 +25,11 @@ from .. import _native
 from ..analysis.beat_analyzer import BeatAnalyzer, queue_frame_series
 from ..analysis.chorus_regions import detect_chorus_regions
 from ..analysis.features_cache import TrackFeatureCache, build_feature_cache
+from .. import config as _config
 from ..config import get_config
+from ..config.auto_profile import (PROFILE_NAMES, apply_profile_overrides, build_auto_profile_overrides, build_style_weight_overrides,
+                                   derive_alignment_overrides, derive_smart_cut_overrides, estimate_style, resolve_smart_cut_intent,
+                                   should_apply_duration_overrides)
 from ..cutting.refine import CutContext, CutPoint, CutRefineResult, finalize_cut_points
 from ..detectors.pure_vocal_pause_detector import PureVocalPauseDetector, _bool_runs
 from .enhanced_vocal_separator import EnhancedVocalSeparator, SeparationResult
@@ -49,6 +53,15 @@ def _remove_true_runs(mask: np.ndarray, max_len: int) -> np.ndarray:
     return out
 
 
+def host_vocal_coverage(mono: np.ndarray) -> float:
+    """The reference's coverage formula on the host (`seamless_splitter.py:884-889`): the yardstick of `ac_abs_peak_coverage`."""
+    mono = np.asarray(mono, dtype=np.float32)
+    peak = float(np.max(np.abs(mono))) if mono.size else 0.0
+    if peak <= 1e-9:
+        return 0.0
+    return float(np.mean(np.abs(mono) >= max(peak * 0.03, 1e-5)))
+
+
 PRECISION_GUARD_AVG_MS = 150.0     # reference `seamless_splitter.py:66-67`
 PRECISION_GUARD_P95_MS = 220.0
 
@@ -68,6 +81,8 @@ class SeamlessSplitter:
         self.beat_analyzer = BeatAnalyzer(sample_rate, ctx=self._hip)
         self._last_guard_adjustments_raw: list = []
         self._last_suppressed_cut_points: list = []
+        self._last_auto_profile_meta: Optional[Dict] = None
+        self._last_intent_meta: Optional[Dict] = None
 
     def _context(self) -> "_native.Context":
         if self._hip is None:
@@ -77,7 +92,7 @@ class SeamlessSplitter:
     # ------------------------------------------------------------------------------------------
     def split_track(self, original_audio: np.ndarray, mode: str = "v2.2_mdd", *, audio_dev=None, separation_gate=None,
                     unet_stream=None, beat_analysis: bool = False, hybrid_density: Optional[str] = None, input_path: str = "",
-                    output_dir: str = "") -> Dict:
+                    output_dir: str = "", smart_cut: Optional[bool] = None) -> Dict:
         """Steps 2-9 of SURVEY.md §3.1 on an in-memory mono float32 track at `sample_rate`.
         `separation_gate` (a lock shared by the workers of a `batch.TrackPipeline`) and `unet_stream` (the pipeline's one U-Net
         stream): with both, this track's separation is queued on that stream under the lock and the lock is released as soon as it is
@@ -94,10 +109,16 @@ class SeamlessSplitter:
         `hybrid_density` ("low" / "medium" / "high") overrides `hybrid_mdd.beat_cut_density` for a `hybrid_mdd` track.
         Mode `vocal_separation` separates and detects nothing: `_split_vocal_separation`.
         `input_path` / `output_dir` reach the VPBD detector as `input_path` / `asr_output_dir` and name nothing else (`vpbd_asr`: where the 16 kHz ASR copy of the vocal stem is written and
-        what it is named after; empty: no file, the provider gets the samples only)."""
+        what it is named after; empty: no file, the provider gets the samples only).
+        `smart_cut`: the smart-cut intent and AutoProfile runtime (`_apply_smart_cut_runtime`) of a `vpbd_acoustic` / `vpbd_asr`
+        track.  None (the default): it runs when the runtime configuration holds a `smart_cut.*` key as the call starts
+        (`separate_and_segment(segments=, alignment=)` puts them there); True: it runs; False: it does not.  Where it does not run
+        the track is split on the configuration as it stands.  Where it does, its overrides are applied between the feature cache
+        and the detection, the result carries `intent` (and `auto_profile` for profile `auto`), and the runtime configuration is
+        put back as it was found when the call returns or raises.  Not with a gate or a U-Net stream: the configuration is global
+        to the process and the workers of a `batch.TrackPipeline` share it."""
         if mode not in self.SUPPORTED_MODES:
             raise NotImplementedError(f"mode {mode!r}: only the v2.2_mdd / v2.1 path is built this round")
-        sr = self.sample_rate
         if original_audio is None or len(original_audio) == 0 or np.shape(original_audio)[-1] == 0:
             raise ValueError("split_track needs a non-empty mono track")
         if mode == "librosa_onset":
@@ -114,6 +135,35 @@ class SeamlessSplitter:
             if separation_gate is not None or unet_stream is not None:
                 raise ValueError("hybrid_mdd tracks are split one at a time (no separation gate / U-Net stream)")
             return self._split_hybrid_mdd(original_audio, audio_dev, hybrid_density)
+        args = (original_audio, mode, audio_dev, separation_gate, unet_stream, beat_analysis, input_path, output_dir)
+        if not self._smart_cut_active(mode, smart_cut):
+            self._last_auto_profile_meta = self._last_intent_meta = None
+            return self._split_pause_modes(*args, smart_cut=False)
+        if separation_gate is not None or unet_stream is not None:
+            raise ValueError("smart-cut tracks are split one at a time (no separation gate / U-Net stream): their overrides go "
+                             "into the runtime configuration, which the workers of a pipeline share")
+        saved = _config.snapshot()
+        try:
+            return self._split_pause_modes(*args, smart_cut=True)
+        finally:
+            _config.restore(saved)              # one track's profile never colours the next
+
+    @staticmethod
+    def _smart_cut_active(mode: str, smart_cut: Optional[bool]) -> bool:
+        """Whether this track runs the smart-cut runtime: only a VPBD mode, and only when asked - by the flag, or by a `smart_cut`
+        key among the runtime overrides.  (The reference runs it on every VPBD track)"""
+        if mode not in ("vpbd_acoustic", "vpbd_asr"):
+            if smart_cut:
+                raise ValueError(f"smart_cut=True: mode {mode!r} has no smart-cut runtime (vpbd_acoustic / vpbd_asr have)")
+            return False
+        if smart_cut is not None:
+            return bool(smart_cut)
+        return any(k == "smart_cut" or k.startswith("smart_cut.") for k in _config.snapshot())
+
+    def _split_pause_modes(self, original_audio: np.ndarray, mode: str, audio_dev, separation_gate, unet_stream, beat_analysis: bool,
+                           input_path: str, output_dir: str, *, smart_cut: bool) -> Dict:
+        """`split_track` for `v2.2_mdd`, `v2.1` and the VPBD modes, after its argument checks."""
+        sr = self.sample_rate
         stereo = np.ndim(original_audio) == 2
         t0 = time.perf_counter()
         sep: SeparationResult = self.separator.separate_for_detection(original_audio, gpu_context=None, audio_dev=audio_dev,
@@ -140,8 +190,11 @@ class SeamlessSplitter:
             result.update({"vocal_track_stereo": sep.vocal_track_stereo, "instrumental_track_stereo": sep.instrumental_track_stereo,
                            "mono_mix": sep.mono_mix})
         if is_vpbd:
-            # reference `:362-408`.  The smart_cut intent / AutoProfile runtime overrides applied at `:349` are
-            # product configuration policy (out of scope): VPBD runs on the base configuration.
+            # reference `:349`: intent, profile and duration overrides go into the runtime configuration ahead of the detection
+            # (here only where asked for: `_smart_cut_active`); then `:362-408`
+            auto_profile_meta = None
+            if smart_cut:
+                auto_profile_meta = self._apply_smart_cut_runtime(cache, vocal_track=vocal_track, vocal_dev=state.get("vocal"))
             vpbd = self.vpbd_detector.detect(mode=mode, vocal_track=vocal_track, original_audio=original_audio,
                                              pure_vocal_detector=self.pure_vocal_detector, feature_cache=cache,
                                              vad_segments=sep.vad_segments, input_path=input_path, asr_output_dir=output_dir,
@@ -156,6 +209,8 @@ class SeamlessSplitter:
             if not cut_candidates:
                 result.update({"sample_boundaries": [0, len(original_audio)], "note": "no_vpbd_candidates",
                                "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": 0.0}})
+                if auto_profile_meta is not None:       # `_create_single_segment_result` (`:2742-2744`) carries this block alone
+                    result["auto_profile"] = auto_profile_meta
                 result.update(self._single_segment_fields(vocal_track, len(original_audio), state.get("vocal")))
                 self._beat_analysis_block(beat_pending, original_audio, cache, result)
                 return result
@@ -225,8 +280,91 @@ class SeamlessSplitter:
                        "precision_guard_ok": bool(stats["avg_shift_ms"] <= PRECISION_GUARD_AVG_MS and stats["p95_shift_ms"] <= PRECISION_GUARD_P95_MS),
                        "precision_guard_threshold_ms": {"avg": PRECISION_GUARD_AVG_MS, "p95": PRECISION_GUARD_P95_MS},
                        "timings": {"separate_s": t_sep, "detect_s": t_det, "finalize_s": t_fin}})
+        if is_vpbd and smart_cut:           # `:761-765`
+            if auto_profile_meta is not None:
+                result["auto_profile"] = auto_profile_meta
+            if self._last_intent_meta is not None:
+                result["intent"] = dict(self._last_intent_meta)
         self._beat_analysis_block(beat_pending, original_audio, cache, result)
         return result
+
+    # ---- smart-cut intent and AutoProfile (reference `seamless_splitter.py:772-893`) ----------------------------------
+    COVERAGE_ON_DEVICE = True           # the vocal coverage of a resident stem comes from `ac_abs_peak_coverage`
+
+    def _apply_smart_cut_runtime(self, feature_cache: Optional[TrackFeatureCache], *, vocal_track: Optional[np.ndarray] = None,
+                                 vocal_dev=None) -> Optional[Dict]:
+        """The `smart_cut` section -> runtime overrides, written in one `set_runtime_config` ahead of the boundary detection:
+        the intent (with the keys the caller set on purpose), the duration knobs where the intent moves them, the profile
+        (`auto`: vocal coverage -> `estimate_style` -> the blended profile; a name; an unknown one: pop, with a warning), and on
+        top of the profile's phrase weights the alignment.  -> the AutoProfile record (None for a named profile); it and the
+        intent record are kept in `_last_auto_profile_meta` / `_last_intent_meta`."""
+        smart_cfg = get_config("smart_cut", {}) or {}
+        if not isinstance(smart_cfg, dict):
+            smart_cfg = {}
+        stated = _config.get_runtime_override_keys()
+        intent = resolve_smart_cut_intent(smart_cfg, explicit_keys=stated)
+        profile = str(intent.get("profile", "auto") or "auto").strip().lower()
+        overrides: Dict = {}
+        if should_apply_duration_overrides(smart_cfg, explicit_keys=stated):
+            overrides.update(derive_smart_cut_overrides(smart_cfg, explicit_keys=stated))
+        auto_meta: Optional[Dict] = None
+        if profile == "auto":
+            self._attach_vocal_coverage(feature_cache, vocal_track, vocal_dev=vocal_dev)
+            picked = build_auto_profile_overrides(estimate_style(feature_cache), cut_style="natural")
+            auto_meta = dict(picked.get("meta.auto_profile", {}))
+            overrides.update(picked)
+            logger.info("[AutoProfile] style=%s confidence=%.3f bpm=%s alignment=%s", auto_meta.get("style"),
+                        float(auto_meta.get("confidence") or 0.0), auto_meta.get("bpm"), intent.get("alignment"))
+        else:
+            if profile not in PROFILE_NAMES:
+                logger.warning("[AutoProfile] unknown smart_cut.profile=%s; falling back to pop", profile)
+                profile = "pop"
+            overrides.update(apply_profile_overrides(profile))
+            overrides.update(build_style_weight_overrides(profile, cut_style="natural"))
+            overrides["meta.profile"] = profile
+        by_alignment = derive_alignment_overrides(intent.get("alignment", 0.5), self._phrase_weights_from_overrides(overrides),
+                                                  alignment_poles=get_config("phrase_boundary.alignment_poles", None))
+        overrides.update(by_alignment)
+        intent = dict(intent)
+        intent["applied_overrides"] = sorted(k for k in by_alignment if not k.startswith("meta."))
+        if auto_meta is not None:
+            auto_meta["alignment"] = {"value": intent.get("alignment"), "raw": intent.get("alignment_raw")}
+        overrides["meta.intent"] = intent
+        _config.set_runtime_config(overrides)
+        self._last_auto_profile_meta = auto_meta
+        self._last_intent_meta = intent
+        return auto_meta
+
+    @staticmethod
+    def _phrase_weights_from_overrides(overrides: Dict) -> Dict[str, float]:
+        """The eight phrase-boundary weights as the profile left them: from `overrides`, else from the configuration."""
+        from ..config.auto_profile import WEIGHT_KEYS
+        flat = {k: f"phrase_boundary.weights.{k}" for k in WEIGHT_KEYS}
+        return {k: float(overrides[f]) if f in overrides else float(get_config(f, 0.0)) for k, f in flat.items()}
+
+    def _attach_vocal_coverage(self, feature_cache: Optional[TrackFeatureCache], vocal_track: Optional[np.ndarray], *,
+                               vocal_dev=None) -> None:
+        """`feature_cache.vocal_coverage_ratio` = the share of the vocal stem's samples at or above max(3 % of its peak, 1e-5), 0.0 for
+        a stem whose peak is at most 1e-9 (`:873-893`).  Nothing without a cache or a stem, for an empty stem, or where the cache
+        carries the ratio already.  A mono stem resident on the device is swept there (`Context.vocal_coverage`: exact peak and
+        count, 16 bytes downloaded); otherwise the host formula.  The attribute is set beside the dataclass's fields, as the
+        reference does: a `dataclasses.replace` copy of the cache does not carry it."""
+        if feature_cache is None or hasattr(feature_cache, "vocal_coverage_ratio"):
+            return
+        if self.COVERAGE_ON_DEVICE and vocal_dev is not None and vocal_dev.dim() == 1:
+            n = int(vocal_dev.numel())
+            if n == 0:
+                return
+            peak, _, count = self._context().vocal_coverage(vocal_dev)
+            coverage = _native.coverage_from(peak, count, n)
+        elif vocal_track is not None:
+            audio = np.asarray(vocal_track, dtype=np.float32)
+            if audio.size == 0:
+                return
+            coverage = host_vocal_coverage(audio if audio.ndim == 1 else np.mean(audio, axis=-1))
+        else:
+            return
+        setattr(feature_cache, "vocal_coverage_ratio", max(0.0, min(1.0, coverage)))
 
     # ---- mode `vocal_separation`: the two stems and nothing else (reference `seamless_splitter.py:958-1036`) ----------
     def _split_vocal_separation(self, original_audio: np.ndarray, audio_dev=None) -> Dict:
