@@ -205,11 +205,13 @@ __device__ inline float ac_polyphase_dot_wave(const float* __restrict__ x, int64
     int64_t t_lo = j0 - (n - 1);                       // q = j0 - t <= n - 1
     if (t_lo < 0) t_lo = 0;
     const int64_t t_hi = j0 < tpp - 1 ? j0 : tpp - 1;  // q >= 0
-    double acc = 0.0;
+    // The sum starts at -0.0, the identity of IEEE addition (+0.0 is not: +0.0 + -0.0 = +0.0), so that it is the sum of the terms
+    // alone and a single tap 1.0 copies x bit for bit, -0.0 included; an empty range (no term at all) is +0.0.
+    double acc = -0.0;
     for (int64_t t = t_lo + lane; t <= t_hi; t += AC_WAVE) acc += (double)row[t] * (double)x[j0 - t];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, AC_WAVE);
-    return (float)acc;
+    return t_lo > t_hi ? 0.f : (float)acc;
 }
 
 // Block-wide sum of doubles for blockDim.x == 256 (4 waves); result valid in every thread.

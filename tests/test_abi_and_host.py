@@ -446,9 +446,9 @@ EXPORT_TESTS = {
     "ac_segment_frame_rms": "test_kernels_edges_gpu::test_segment_frame_rms_edges",
     "ac_segment_sumsq_peak": "test_kernels_edges_gpu::test_segment_sumsq_peak_edges",
     "ac_local_valley": "test_kernels_edges_gpu::test_local_valley_edges",
-    "ac_resample_poly": "test_export_loader::test_resample_poly_kernel_vs_oracle",
+    "ac_resample_poly": "test_resample_pcm_edges_gpu::test_resample_poly_same_taps",
     "ac_resample_poly_segments": "test_kernels_edges_gpu::test_resample_poly_segments_edges",
-    "ac_pack_pcm24": "test_export_loader::test_pack_pcm24_kernel_vs_host",
+    "ac_pack_pcm24": "test_resample_pcm_edges_gpu::test_pack_pcm24_known_answers_in_every_lane_and_in_the_tail",
     "ac_silero_frontend": "test_silero_kernels_gpu::test_frontend_against_float64",
     "ac_silero_lstm": "test_silero_kernels_gpu::test_lstm_synthetic_gates",
     "ac_silero_out": "test_silero_kernels_gpu::test_out_against_float64",

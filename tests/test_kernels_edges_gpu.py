@@ -208,7 +208,8 @@ def test_resample_poly_segments_edges(hip_ctx, track, up, down):
     """Every segment is `resample_poly` of the segment alone, bit for bit (ac_vad.hip: scipy.signal.resample_poly on the segment
     alone), and within 2e-6 of the float64 oracle (the float32 polyphase dot against float64 scipy: the precedent of
     `test_resample_poly_kernel_vs_oracle`); bucket padding is exactly 0.0.  Lengths 0, 1, 2, 159, 160, 441, 442 and one whose output
-    is an exact multiple of the 4096 bucket; buckets 0 and 4096; up == down (a copy)."""
+    is an exact multiple of the 4096 bucket; buckets 0 and 4096; up == down (a copy).  The 2e-6 covers only the filter DESIGN
+    difference with the oracle; the arithmetic is held by the same-taps tests of test_resample_pcm_edges_gpu.py."""
     import math
     g = math.gcd(up, down); u, d = up // g, down // g
     n = len(track)
