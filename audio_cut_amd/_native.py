@@ -55,6 +55,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so asr ABI version mismatch")
     if lib.ac_profile_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so profile ABI version mismatch")
+    if lib.ac_final_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so final-layer ABI version mismatch")
     _lib = lib
     return lib
 
@@ -166,6 +168,12 @@ PROFILE_SIGNATURES = {
     "ac_profile_abi_version": (C.c_int, []),
     "ac_abs_peak_coverage": (C.c_int, [_P, _P, _I64, C.c_double, C.c_double, _P, _P, _P, _P]),
 }
+# include/audiocut_hip_final.h: the U-Net's last TDF layer with the final 1x1 conv in its epilogue, exported by the same library and
+# versioned on its own
+FINAL_SIGNATURES = {
+    "ac_final_abi_version": (C.c_int, []),
+    "ac_tdf_linear_final_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, C.c_float, _P, _P]),
+}
 # 4 * AC_PROFILE_BLOCK * AC_PROFILE_MAX_BLOCKS: the samples one step of the largest grid of ac_abs_peak_coverage covers (from
 # twice this many on, every thread of either sweep goes round its loop at least twice)
 PROFILE_GRID_SAMPLES = 4 * 256 * 2048
@@ -182,7 +190,8 @@ def coverage_from(peak: float, count: int, n: int) -> float:
 
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
-                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items()):
+                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items(),
+                              *FINAL_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -1064,6 +1073,40 @@ class Context:
         _check(self.lib.ac_tdf_linear_f16x3(self._h, _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(resid), _ptr(out),
                                             b * c * t, n_out, k, t, c, float(w_unscale), pi, po, _stream()))
         return out
+
+    @staticmethod
+    def tdf_final_tileable(c: int, t: int, k: int, n_out: int, c_out: int) -> bool:
+        """Shapes ac_tdf_linear_final_f16x3 tiles (csrc/ac_gemm.hip; keep in step with its AC_REQUIRE): all 48 channels x 2 time rows x 192
+        columns per workgroup, K in stages of 32, at most 4 output channels of the final conv."""
+        return c == 48 and t > 0 and t % 2 == 0 and k > 0 and k % 32 == 0 and n_out > 0 and n_out % 192 == 0 and 1 <= c_out <= 4
+
+    def tdf_linear_final_f16x3(self, x: torch.Tensor, w_packed: torch.Tensor, n_out: int, scale: torch.Tensor, shift: torch.Tensor,
+                               w_unscale: float, resid: torch.Tensor, final_w: torch.Tensor, final_b: torch.Tensor,
+                               in_amax: Optional[torch.Tensor] = None, want_y: bool = False):
+        """The block's second TDF layer (tdf_linear_f16x3 with the residual) and the graph's final 1x1 conv (conv1x1_small, no ReLU)
+        in one kernel: [B, C, T, K] -> the spectrogram [B, C_out, T, n_out], bit-identical to the two calls; the [B, C, T, n_out]
+        tensor between them is written (and returned second) only with `want_y`.  Shapes the kernel cannot tile raise NativeError."""
+        if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+            raise NativeError("tdf_linear_final_f16x3 expects a contiguous float32 NCHW tensor")
+        b, c, t, k = x.shape
+        w2 = final_w.reshape(final_w.shape[0], -1)
+        if w2.shape[1] != c or not w2.is_contiguous() or w2.dtype != torch.float32:
+            raise NativeError("tdf_linear_final_f16x3: final weight must be [C_out, C(,1,1)] contiguous float32")
+        c_out = w2.shape[0]
+        if self.tdf_final_tileable(c, t, k, int(n_out), c_out):      # else the library refuses the shape itself
+            _packed("tdf_linear_final_f16x3", w_packed, _linear_packed_bytes(int(n_out), k, 0))
+        _packed("tdf_linear_final_f16x3 (bias)", final_b, c_out * 4)
+        _packed("tdf_linear_final_f16x3 (scale)", scale, c * 4)
+        _packed("tdf_linear_final_f16x3 (shift)", shift, c * 4)
+        if resid is None or resid.shape != (b, c, t, n_out) or not resid.is_contiguous() or resid.dtype != torch.float32:
+            raise NativeError("tdf_linear_final_f16x3: residual must match the TDF layer's output")
+        spec = torch.empty((b, c_out, t, n_out), dtype=torch.float32, device=self.device)
+        y = torch.empty((b, c, t, n_out), dtype=torch.float32, device=self.device) if want_y else None
+        pi, _ = self._amax_args(b, in_amax, None, t, t)
+        _check(self.lib.ac_tdf_linear_final_f16x3(self._h, _ptr(x), _ptr(w_packed), _ptr(scale), _ptr(shift), _ptr(resid), _ptr(w2),
+                                                  _ptr(final_b), _ptr(spec), _ptr(y), b * c * t, n_out, k, t, c, c_out,
+                                                  float(w_unscale), pi, _stream()))
+        return (spec, y) if want_y else spec
 
     def tdf_small_fused(self, x: torch.Tensor, w1_packed: torch.Tensor, w2_packed: torch.Tensor, hidden: int, scale1: torch.Tensor,
                         shift1: torch.Tensor, scale2: torch.Tensor, shift2: torch.Tensor,

@@ -197,10 +197,18 @@ class _Block(nn.Module):
             probe.append((e0, e1, 2.0 * x.shape[0] * x.shape[1] * x.shape[1] * 9 * x.shape[2] * x.shape[3]))
         return y, ay
 
-    def _tdf(self, x: torch.Tensor, ax: torch.Tensor, hip, tape: _AmaxTape):
+    def takes_final(self, c: int, t: int, final_w: torch.Tensor) -> bool:
+        """Can this block's second TDF layer carry the graph's final 1x1 conv in its epilogue (ac_tdf_linear_final_f16x3: wide TDF
+        layers, all 48 channels in one tile)?  Otherwise the two kernels run one after the other - same bits either way."""
+        from .._native import Context
+        return (hasattr(self, "lwp0") and c % 16 == 0 and t % 8 == 0 and final_w.shape[1] == c
+                and Context.tdf_final_tileable(c, t, self.lw1.shape[1], self.lw1.shape[0], final_w.shape[0]))
+
+    def _tdf(self, x: torch.Tensor, ax: torch.Tensor, hip, tape: _AmaxTape, final=None):
         """x + relu(bn(linear(relu(bn(linear(x)))))) over the frequency axis: two fused GEMM kernels on the f16 matrix cores
         (ac_tdf_linear_f16x3: + per-channel affine + ReLU (+ residual)), or one exact-float32 kernel for the narrow pairs of the
-        deep levels (ac_tdf_small_fused)."""
+        deep levels (ac_tdf_small_fused).  `final` = (weight, bias) of the graph's final 1x1 conv (only where `takes_final`): the
+        second layer applies it in its epilogue and the spectrogram is returned in place of the block's output (no maxima)."""
         from .._native import NativeError
         rows = x.shape[0] * x.shape[1] * x.shape[2]
         ay = tape.new(x.shape[2])
@@ -208,6 +216,9 @@ class _Block(nn.Module):
             ah = tape.new(x.shape[2])
             h = hip.tdf_linear_f16x3(x, self.lwp0, self.lw0.shape[0], self.ls0.view(-1), self.lb0.view(-1), self._l_unscale[0],
                                      in_amax=ax, out_amax=ah)
+            if final is not None:
+                return hip.tdf_linear_final_f16x3(h, self.lwp1, self.lw1.shape[0], self.ls1.view(-1), self.lb1.view(-1),
+                                                  self._l_unscale[1], x, final[0], final[1], in_amax=ah), None
             y = hip.tdf_linear_f16x3(h, self.lwp1, self.lw1.shape[0], self.ls1.view(-1), self.lb1.view(-1), self._l_unscale[1], resid=x,
                                      in_amax=ah, out_amax=ay)
             return y, ay
@@ -217,9 +228,9 @@ class _Block(nn.Module):
             return y, ay
         raise NativeError(f"TDF of shape {tuple(x.shape)} -> {self.lw0.shape[0]} is not tileable by the HIP kernels")
 
-    def forward_hip(self, x: torch.Tensor, ax: torch.Tensor, hip, tape: _AmaxTape, probe=None, first=None):
+    def forward_hip(self, x: torch.Tensor, ax: torch.Tensor, hip, tape: _AmaxTape, probe=None, first=None, final=None):
         """`first` = (w1, b1, gain, offs) of the graph's first 1x1 convolution: fused into this block's first 3x3 conv (x is the
-        spectrogram, ax its per-item max; gain / offs bound the generated tensor)."""
+        spectrogram, ax its per-item max; gain / offs bound the generated tensor).  `final`: see `_tdf`."""
         start = 0
         if first is not None:
             if probe is not None:
@@ -240,7 +251,7 @@ class _Block(nn.Module):
             start = 1
         for j in range(start, self.l):
             x, ax = self._conv(x, ax, j, hip, tape, probe)
-        return self._tdf(x, ax, hip, tape)
+        return self._tdf(x, ax, hip, tape, final)
 
 
 class TfcTdfNet(nn.Module):
@@ -348,6 +359,13 @@ class TfcTdfNet(nn.Module):
         if self.block_tap is not None: self.block_tap("bottleneck", x)
         for i in range(n):
             x, ax = self._up(x, ax, i, hip, skips.pop(), tape)
-            x, ax = self.dec[i].forward_hip(x, ax, hip, tape, self.conv_probe)
+            # the last block's second TDF layer carries the final 1x1 conv in its epilogue where the shape fits its 48-channel tile;
+            # a block tap needs the block's own output, so with one set the two kernels run one after the other (the same bits)
+            final = None
+            if i == n - 1 and self.block_tap is None and self.dec[i].takes_final(x.shape[1], x.shape[2], self.final_w):
+                final = (self.final_w, self.final_b)
+            x, ax = self.dec[i].forward_hip(x, ax, hip, tape, self.conv_probe, final=final)
+            if final is not None:
+                return x
             if self.block_tap is not None: self.block_tap(f"dec{i}", x)
         return hip.conv1x1_small(x, self.final_w, self.final_b, relu=False)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What runs after a track's U-Net: from a rocprofv3 --kernel-trace rocpd database of `bench.py --pipeline-depth 1`, every kernel and
-copy between the LAST U-Net kernel of the last forward of a track (k_conv1x1_small) and the first kernel of the next track's U-Net
+copy between the LAST U-Net kernel of the last forward of a track (the last TDF layer with the final 1x1 conv in its epilogue, the
+96-row instantiation of k_tdf_linear_f16x3; k_conv1x1_small in traces of builds before it) and the first kernel of the next track's U-Net
 (or the end of the trace), with the idle gap in front of each one.  This is the exposed tail `single_stream_latency_ms` sees.
 Usage: tools/track_tail_timeline.py <results.db> [track index from the end = 1]"""
 import sqlite3, sys
@@ -16,9 +17,9 @@ try:
 except sqlite3.Error:
     pass
 rows.sort()
-lasts = [i for i, r in enumerate(rows) if "k_conv1x1_small" in r[2]]
+lasts = [i for i, r in enumerate(rows) if "k_conv1x1_small" in r[2] or "k_tdf_linear_f16x3ILi6ELb1ELi96" in r[2]]
 firsts = [i for i, r in enumerate(rows) if "k_mdx_stft" in r[2]]
-# forwards come in pairs per track (two sub-batches of 32 items): the track's last forward is every second k_conv1x1_small
+# forwards come in pairs per track (two sub-batches of 32 items): the track's last forward is every second one of these
 ends = lasts[1::2] if len(lasts) % 2 == 0 else lasts
 i0 = ends[-back]
 nxt = [f for f in firsts if f > i0]
