@@ -57,6 +57,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so profile ABI version mismatch")
     if lib.ac_final_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so final-layer ABI version mismatch")
+    if lib.ac_load_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so loader ABI version mismatch")
     _lib = lib
     return lib
 
@@ -174,6 +176,12 @@ FINAL_SIGNATURES = {
     "ac_final_abi_version": (C.c_int, []),
     "ac_tdf_linear_final_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, C.c_float, _P, _P]),
 }
+# include/audiocut_hip_load.h: the loader's decode (file bytes -> the resident float32 track), exported by the same library and
+# versioned on its own
+LOAD_SIGNATURES = {
+    "ac_load_abi_version": (C.c_int, []),
+    "ac_decode_pcm": (C.c_int, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P, _P]),
+}
 # 4 * AC_PROFILE_BLOCK * AC_PROFILE_MAX_BLOCKS: the samples one step of the largest grid of ac_abs_peak_coverage covers (from
 # twice this many on, every thread of either sweep goes round its loop at least twice)
 PROFILE_GRID_SAMPLES = 4 * 256 * 2048
@@ -191,7 +199,7 @@ def coverage_from(peak: float, count: int, n: int) -> float:
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
                               *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items(),
-                              *FINAL_SIGNATURES.items()):
+                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -566,6 +574,28 @@ class Context:
         out = torch.empty(3 * n + 3, dtype=torch.uint8, device=self.device)
         _check(self.lib.ac_pack_pcm24(self._h, _ptr(x), n, _ptr(out), _stream()))
         return out[: 3 * n].cpu().numpy()
+
+    def decode_pcm(self, raw_dev: torch.Tensor, info, layout: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, int]:
+        """The sample bytes of a WAV file, resident as a uint8 tensor of at least `info.data_bytes` bytes, -> (track, nonfinite):
+        `utils.wav_reader.decode_host(raw, info, layout)` bit for bit (`ac_decode_pcm`, include/audiocut_hip_load.h) and the number of
+        samples that are NaN or infinite (one 8-byte download; always 0 for integer PCM).  layout 0: float32 [n_frames], the channel
+        mean; layout 1: float32 [channels, n_frames], or the rows of a given `out` [channels, stride >= n_frames], of which only the
+        first n_frames elements are written."""
+        n, ch = int(info.n_frames), int(info.channels)
+        if raw_dev.dtype != torch.uint8 or raw_dev.device != self.device or raw_dev.dim() != 1 or raw_dev.numel() < int(info.data_bytes):
+            raise NativeError("decode_pcm: expected a 1-D uint8 tensor on the context's device holding the file's data bytes")
+        if layout not in (0, 1):
+            raise ValueError(f"decode_pcm: unknown layout {layout!r}")
+        shape = (ch, n) if layout == 1 else (n,)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or out.device != self.device or out.dim() != len(shape) or out.shape[-1] < n
+              or (layout == 1 and out.shape[0] != ch)):
+            raise NativeError(f"decode_pcm: `out` must be a float32 tensor of shape {shape} (or wider rows) on the context's device")
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        _check(self.lib.ac_decode_pcm(self._h, _ptr(raw_dev), n, ch, int(info.format_code), int(layout), _ptr(out),
+                                      int(out.shape[-1]) if layout == 1 else n, _ptr(count), _stream()))
+        return out, int(count.item())
 
     # -- post-path boundary policy (SURVEY.md 8(f) row 1) ----------------------------------------------
     def segment_frame_rms(self, x: torch.Tensor, seg_start: np.ndarray, seg_end: np.ndarray, frame: int, hop: int, center: bool = True):

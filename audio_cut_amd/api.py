@@ -14,8 +14,13 @@ with a lyrics provider's timeline: `<name>_vocal_for_asr.wav`, the 16 kHz 16-bit
 `hybrid_mdd` (phrase-pause cuts snapped to beats in chorus bars: mix and vocal segments named `..._lib_D.D` where a segment ends on
 a beat, and the full vocal) and `vocal_separation` (the two stems and nothing else: `<name>_vocal_D.D.wav` and
 `<name>_instrumental_D.D.wav`, no detection, no segments).
-Loader: PCM WAV / .npy, channel mean like `librosa.load(mono=True)`; a file whose rate differs from `audio.sample_rate`
-is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
+Loader: WAV / .npy.  WAVs are read by `utils/wav_reader.py`: PCM of 8, 16, 24 and 32 bits and IEEE float of 32 and 64, plain or
+WAVE_FORMAT_EXTENSIBLE, 1 to 8 channels; companded and compressed files, RF64 and RIFX are refused by name ("Input
+files").  With `audio.gpu_decode` (default true) a `.wav` is decoded on the device (`load_audio_device`): the file's own bytes are
+read into pinned memory and uploaded, and one kernel (`ac_decode_pcm`) leaves the float32 track resident - bit for bit what
+`load_audio_mono` / `load_audio_stereo` decode on the host, which `.npy` input and `audio.gpu_decode: false` still go through.  The
+channel mean is `librosa.load(mono=True)`'s; a float file holding a NaN or an infinity is refused.  A file whose rate differs from
+`audio.sample_rate` is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
 `<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all PCM_24 packed on the GPU (`ac_pack_pcm24`).
@@ -31,7 +36,6 @@ round differently, so the same file may give different cut samples with 1 and 2 
 from __future__ import annotations
 
 import json
-import wave
 from pathlib import Path
 from typing import Any, Dict, Mapping, Optional, Sequence
 
@@ -42,40 +46,28 @@ from .config.auto_profile import resolve_smart_cut_intent
 from .core.seamless_splitter import SeamlessSplitter
 from .lyrics.models import LyricsTimeline
 from .lyrics.segment_attach import attach_lyrics_to_segments
+from .utils.wav_reader import LAYOUT_MONO, LAYOUT_PLANAR, channel_mean, read_wav, read_wav_bytes, read_wav_info
 
 
 def _read_wav(p: Path) -> tuple:
-    """PCM16/24/32 WAV -> (float32 [frames, channels] in [-1, 1], sample_rate)."""
-    with wave.open(str(p), "rb") as w:
-        sr, ch, width, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
-        raw = w.readframes(n)
-    if width == 2:
-        data = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
-    elif width == 3:
-        b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
-        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
-        v = np.where(v & 0x800000, v - 0x1000000, v)
-        data = v.astype(np.float32) / 8388608.0
-    elif width == 4:
-        data = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
-    else:
-        raise ValueError(f"unsupported WAV sample width {width}")
-    return data.reshape(-1, ch), sr
+    """PCM 8/16/24/32 or float 32/64 WAV, plain or WAVE_FORMAT_EXTENSIBLE -> (float32 [frames, channels], sample_rate).  PCM lies in
+    [-1, 1); float samples pass as they are."""
+    return read_wav(p)
 
 
 def load_audio_mono(path: str) -> tuple:
-    """PCM16/24/32 WAV or .npy -> (mono float32 in [-1, 1], sample_rate).  Channel mean like `librosa.load(mono=True)`."""
+    """WAV (`utils/wav_reader.py`) or .npy -> (mono float32, sample_rate).  Channel mean like `librosa.load(mono=True)`: the float32
+    sum in channel order over float32(channels), which is `np.mean(axis=1)` bit for bit for up to six channels."""
     p = Path(path)
     if p.suffix.lower() == ".npy":
         arr = np.load(p)
         return (np.mean(arr, axis=0) if arr.ndim == 2 else arr).astype(np.float32), 44100
     data, sr = _read_wav(p)
-    ch = data.shape[1]
-    return np.mean(data, axis=1).astype(np.float32) if ch > 1 else data[:, 0].copy(), sr
+    return channel_mean(data), sr
 
 
 def load_audio_stereo(path: str) -> tuple:
-    """PCM16/24/32 WAV or .npy -> (planar float32 (2, N) in [-1, 1], sample_rate) for `audio.channels: 2`.  A mono file (a 1-D
+    """WAV or .npy -> (planar float32 (2, N), sample_rate) for `audio.channels: 2`.  A mono file (a 1-D
     or (1, N) array, a 1-channel WAV) is duplicated to both channels; more than two channels is refused.  `.npy` arrays are
     (channels, N) like the mono loader reads them, at 44100 Hz."""
     p = Path(path)
@@ -92,6 +84,36 @@ def load_audio_stereo(path: str) -> tuple:
     if arr.shape[0] != 2:
         raise ValueError(f"{p}: {arr.shape[0]} channels; audio.channels: 2 takes mono or stereo input")
     return np.ascontiguousarray(arr, dtype=np.float32), sr
+
+
+def load_audio_device(path: str, hip, channels: int = 1) -> tuple:
+    """WAV -> (the track resident on `hip`'s device, sample_rate) without decoding on the host: the header walk
+    (`read_wav_info`), one read of the sample bytes straight into pinned memory, one asynchronous copy on the current stream and
+    one `ac_decode_pcm`.  `channels=1`: float32 [N], the channel mean (`load_audio_mono`'s bits); `channels=2`: planar float32
+    [2, N] (`load_audio_stereo`'s: a mono file goes to both channels, more than two are refused).  A float file with a NaN or an
+    infinity in it is refused with the count, as `librosa.load` refuses it (`valid_audio`).  Pinned staging was measured against
+    pageable memory (the loader) and is 3 to 4 times faster for a stereo track."""
+    import torch
+    p = Path(path)
+    channels = _check_channels(channels)
+    info = read_wav_info(p)
+    if channels == 2 and info.channels > 2:
+        raise ValueError(f"{p}: {info.channels} channels; audio.channels: 2 takes mono or stereo input")
+    staged = torch.empty(info.data_bytes, dtype=torch.uint8, pin_memory=True)
+    read_wav_bytes(p, info, into=staged.numpy())
+    with torch.cuda.device(hip.device):
+        raw_dev = staged.to(hip.device, non_blocking=True)      # the caching host allocator keeps the block until the copy has run
+        if channels == 1:
+            track, bad = hip.decode_pcm(raw_dev, info, LAYOUT_MONO)
+        elif info.channels == 2:
+            track, bad = hip.decode_pcm(raw_dev, info, LAYOUT_PLANAR)
+        else:
+            track = torch.empty((2, info.n_frames), dtype=torch.float32, device=hip.device)
+            _, bad = hip.decode_pcm(raw_dev, info, LAYOUT_MONO, out=track[0])
+            track[1].copy_(track[0])
+    if bad:
+        raise ValueError(f"{p}: {bad} samples are NaN or infinite")
+    return track, info.sample_rate
 
 
 def _check_channels(value: Any) -> int:
@@ -269,7 +291,15 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     splitter = SeamlessSplitter(sample_rate=sr, device=device)
     hip = splitter._context()
     audio_dev = None
-    if channels == 2:
+    if in_path.suffix.lower() == ".wav" and bool(_config.get_config("audio.gpu_decode", True)):
+        # the file's bytes are decoded on the device (`load_audio_device`); the host copy of the track is one download
+        audio_dev, file_sr = load_audio_device(str(in_path), hip, channels)
+        if file_sr != sr:                     # as below: per channel for two channels, the mono mean for one
+            import torch
+            audio_dev = torch.stack([hip.resample_poly(audio_dev[c].contiguous(), sr, file_sr) for c in range(2)]) if channels == 2 \
+                else hip.resample_poly(audio_dev, sr, file_sr)
+        audio = audio_dev.cpu().numpy()
+    elif channels == 2:
         audio, file_sr = load_audio_stereo(str(in_path))
         if file_sr != sr:                     # each channel on its own; detection then reads the mean of the resampled channels
             import torch
@@ -476,9 +506,8 @@ def _track_seconds(result: Mapping[str, Any], input_path: Path) -> Optional[floa
         except (TypeError, ValueError):
             pass
     try:
-        with wave.open(str(input_path), "rb") as w:
-            if w.getnframes() and w.getframerate():
-                return w.getnframes() / float(w.getframerate())
+        info = read_wav_info(input_path)
+        return info.n_frames / float(info.sample_rate)
     except Exception:
         pass
     durations = result.get("segment_durations")
@@ -534,4 +563,4 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
     return manifest
 
 
-__all__ = ["separate_and_segment", "load_audio_mono", "load_audio_stereo", "last_result"]
+__all__ = ["separate_and_segment", "load_audio_mono", "load_audio_stereo", "load_audio_device", "last_result"]

@@ -18,7 +18,8 @@ DEFAULTS: Dict[str, Any] = {
     # the v2.8 intent surface (`unified.yaml:8-14`); read by `SeamlessSplitter._apply_smart_cut_runtime` alone
     "smart_cut": {"segments": "medium", "alignment": "balanced", "profile": "auto", "cut_style": "natural",
                   "target_duration_s": [5.0, 12.0], "lyrics": "auto"},
-    "audio": {"sample_rate": 44100, "channels": 1},
+    # `gpu_decode`: .wav input is decoded on the device from the file's own bytes (`api.load_audio_device`); false: on the host
+    "audio": {"sample_rate": 44100, "channels": 1, "gpu_decode": True},
     "gpu_pipeline": {
         "enable": True, "prefer_device": "cuda", "strict_gpu": False,
         "chunk_seconds": 10.0, "overlap_seconds": 2.5, "halo_seconds": 0.5, "align_hop": 4096,
