@@ -785,32 +785,14 @@ class Context:
             cls._PYIN_TABLES = (thresholds, beta_probs, beta_cum, fact, ek)
         return cls._PYIN_TABLES
 
-    def pyin(self, x: torch.Tensor, sr: int, fmin: float, fmax: float, frame_length: int = 2048, hop: Optional[int] = None,
-             resolution: float = 0.1, max_transition_rate: float = 35.92, switch_prob: float = 0.01, no_trough_prob: float = 0.01):
-        """librosa.pyin on the GPU -> (f0 [frames] float64 with NaN where unvoiced, voiced_flag, voiced_prob), host arrays.
-        CMND curves (ac_yin_f0) -> trough probabilities / pitch-bin observations (ac_pyin_observe) -> Viterbi (ac_pyin_viterbi)."""
+    @staticmethod
+    def pyin_transition_tables(n_bins: int, width: int, switch_prob: float = 0.01):
+        """Banded log-transition tables of librosa.pyin's HMM -> (half, lt_same, lt_cross [n_bins, 2 * half + 1], lt_zero, log_p_init
+        [2 * n_bins]), host float64.  The pitch block is built exactly like librosa.sequence.transition_local(window="triangle",
+        wrap=False) and stored per DESTINATION j: tap d <-> source i = j - half + d; lt_zero = log(0 + tiny) is what librosa's dense
+        matrix holds outside the band."""
         import scipy.signal
-        self._chk_f32(x)
-        hop = frame_length // 4 if hop is None else int(hop)
-        n = x.numel()
-        _, cmnd = self.yin_f0(x, sr, fmin, fmax, frame_length, hop, want_cmnd=True)
-        nf, n_lags = cmnd.shape
-        min_period = max(int(np.floor(sr / fmax)), 1)
-        bps = int(np.ceil(1.0 / resolution))
-        n_bins = int(np.floor(12 * bps * np.log2(fmax / fmin))) + 1
-        thresholds, beta_probs, beta_cum, fact, ek = self._pyin_tables()
         tiny = float(np.finfo(np.float64).tiny)
-        d = lambda a: self.to_device(np.ascontiguousarray(a, dtype=np.float64))
-        logv = torch.empty((nf, n_bins), dtype=torch.float64, device=self.device)
-        logu = torch.empty(nf, dtype=torch.float64, device=self.device)
-        vp = torch.empty(nf, dtype=torch.float64, device=self.device)
-        tabs = [d(thresholds), d(beta_probs), d(beta_cum), d(fact), d(ek)]     # keep the device tables alive across the launch
-        _check(self.lib.ac_pyin_observe(self._h, _ptr(cmnd), nf, n_lags, min_period, float(sr), float(fmin), n_bins, bps,
-                                        _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), _ptr(tabs[4]),
-                                        float(no_trough_prob), tiny, _ptr(logv), _ptr(logu), _ptr(vp), _stream()))
-        # banded log-transition tables, built exactly like librosa.sequence.transition_local(window="triangle", wrap=False)
-        max_semitones = round(max_transition_rate * 12 * hop / sr)
-        width = max_semitones * bps + 1
         half = width // 2
         win = scipy.signal.get_window("triangle", width, fftbins=False)
         base = np.zeros(n_bins)
@@ -830,11 +812,59 @@ class Context:
         lt_same = np.log((1 - switch_prob) * t_in + tiny)
         lt_cross = np.log(switch_prob * t_in + tiny)
         p_init = np.zeros(2 * n_bins); p_init[n_bins:] = 1 / n_bins
+        return half, lt_same, lt_cross, float(np.log(tiny)), np.log(p_init + tiny)
+
+    def pyin_observe(self, cmnd: torch.Tensor, sr: float, fmin: float, min_period: int, n_bins: int, bps: int,
+                     no_trough_prob: float = 0.01):
+        """ac_pyin_observe on CMND rows [frames, lags] (float64, device) -> (logv [frames, n_bins], logu [frames], voiced_prob [frames]),
+        device float64: log(observation + tiny) of the voiced bins, of one unvoiced state, and the clipped voiced mass."""
+        if cmnd.dtype != torch.float64 or cmnd.dim() != 2 or not cmnd.is_cuda:
+            raise NativeError("pyin_observe: cmnd must be a float64 device tensor [frames, lags]")
+        nf, n_lags = cmnd.shape
+        thresholds, beta_probs, beta_cum, fact, ek = self._pyin_tables()
+        tiny = float(np.finfo(np.float64).tiny)
+        d = lambda a: self.to_device(np.ascontiguousarray(a, dtype=np.float64))
+        logv = torch.empty((nf, n_bins), dtype=torch.float64, device=self.device)
+        logu = torch.empty(nf, dtype=torch.float64, device=self.device)
+        vp = torch.empty(nf, dtype=torch.float64, device=self.device)
+        tabs = [d(thresholds), d(beta_probs), d(beta_cum), d(fact), d(ek)]     # keep the device tables alive across the launch
+        _check(self.lib.ac_pyin_observe(self._h, _ptr(cmnd), nf, n_lags, int(min_period), float(sr), float(fmin), int(n_bins), int(bps),
+                                        _ptr(tabs[0]), _ptr(tabs[1]), _ptr(tabs[2]), _ptr(tabs[3]), _ptr(tabs[4]),
+                                        float(no_trough_prob), tiny, _ptr(logv), _ptr(logu), _ptr(vp), _stream()))
+        return logv, logu, vp
+
+    def pyin_viterbi(self, logv: torch.Tensor, logu: torch.Tensor, n_bins: int, half: int, lt_same, lt_cross, lt_zero: float, log_p_init):
+        """ac_pyin_viterbi on device log-observations (logv [frames, n_bins], logu [frames]) and host tables ->
+        (states [frames] int32, ptr [frames, 2 * n_bins] int16 holding uint16 back-pointers; row 0 is never written), device tensors."""
+        nf = logv.shape[0]
+        # the kernel reads the tables by these shapes: a smaller buffer would be read past its end
+        if logv.dtype != torch.float64 or logu.dtype != torch.float64 or tuple(logv.shape) != (nf, n_bins) or tuple(logu.shape) != (nf,):
+            raise NativeError("pyin_viterbi: logv must be float64 [frames, n_bins] and logu float64 [frames]")
+        if (np.shape(lt_same) != (n_bins, 2 * half + 1) or np.shape(lt_cross) != (n_bins, 2 * half + 1)
+                or np.shape(log_p_init) != (2 * n_bins,)):
+            raise NativeError("pyin_viterbi: lt_same / lt_cross must be [n_bins, 2 * half + 1] and log_p_init [2 * n_bins]")
+        d = lambda a: self.to_device(np.ascontiguousarray(a, dtype=np.float64))
         ptr = torch.empty((nf, 2 * n_bins), dtype=torch.int16, device=self.device)
         states = torch.empty(nf, dtype=torch.int32, device=self.device)
-        vt = [d(lt_same), d(lt_cross), d(np.log(p_init + tiny))]
-        _check(self.lib.ac_pyin_viterbi(self._h, _ptr(logv), _ptr(logu), nf, n_bins, half, _ptr(vt[0]), _ptr(vt[1]),
-                                        float(np.log(tiny)), _ptr(vt[2]), _ptr(ptr), _ptr(states), _stream()))
+        vt = [d(lt_same), d(lt_cross), d(log_p_init)]
+        _check(self.lib.ac_pyin_viterbi(self._h, _ptr(logv), _ptr(logu), nf, int(n_bins), int(half), _ptr(vt[0]), _ptr(vt[1]),
+                                        float(lt_zero), _ptr(vt[2]), _ptr(ptr), _ptr(states), _stream()))
+        return states, ptr
+
+    def pyin(self, x: torch.Tensor, sr: int, fmin: float, fmax: float, frame_length: int = 2048, hop: Optional[int] = None,
+             resolution: float = 0.1, max_transition_rate: float = 35.92, switch_prob: float = 0.01, no_trough_prob: float = 0.01):
+        """librosa.pyin on the GPU -> (f0 [frames] float64 with NaN where unvoiced, voiced_flag, voiced_prob), host arrays.
+        CMND curves (ac_yin_f0) -> trough probabilities / pitch-bin observations (ac_pyin_observe) -> Viterbi (ac_pyin_viterbi)."""
+        self._chk_f32(x)
+        hop = frame_length // 4 if hop is None else int(hop)
+        _, cmnd = self.yin_f0(x, sr, fmin, fmax, frame_length, hop, want_cmnd=True)
+        min_period = max(int(np.floor(sr / fmax)), 1)
+        bps = int(np.ceil(1.0 / resolution))
+        n_bins = int(np.floor(12 * bps * np.log2(fmax / fmin))) + 1
+        logv, logu, vp = self.pyin_observe(cmnd, sr, fmin, min_period, n_bins, bps, no_trough_prob)
+        max_semitones = round(max_transition_rate * 12 * hop / sr)
+        half, lt_same, lt_cross, lt_zero, log_p_init = self.pyin_transition_tables(n_bins, max_semitones * bps + 1, switch_prob)
+        states, _ = self.pyin_viterbi(logv, logu, n_bins, half, lt_same, lt_cross, lt_zero, log_p_init)
         st = states.cpu().numpy().astype(np.int64)
         freqs = fmin * 2 ** (np.arange(n_bins) / (12 * bps))
         f0 = freqs[st % n_bins]

@@ -438,9 +438,9 @@ EXPORT_TESTS = {
     "ac_tdf_small_fused": "test_unet_gpu::test_tdf_small_fused_kernel",
     "ac_down2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
     "ac_up2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
-    "ac_pyin_observe": "test_kernels_edges_gpu::test_pyin_edges",
-    "ac_pyin_viterbi": "test_kernels_edges_gpu::test_pyin_edges",
-    "ac_lpc_formants": "test_kernels_edges_gpu::test_lpc_formants_edges",
+    "ac_pyin_observe": "test_pitch_kernels_gpu::test_observe_crafted_rows",
+    "ac_pyin_viterbi": "test_pitch_kernels_gpu::test_viterbi_bit_exact",
+    "ac_lpc_formants": "test_pitch_kernels_gpu::test_lpc_formants_exact",
     "ac_zero_crossing_rate": "test_kernels_edges_gpu::test_zero_crossing_rate_edges",
     "ac_stft2048_spectral": "test_kernels_edges_gpu::test_stft2048_spectral_edges",
     "ac_segment_frame_rms": "test_kernels_edges_gpu::test_segment_frame_rms_edges",
