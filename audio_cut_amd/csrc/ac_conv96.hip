@@ -16,7 +16,6 @@
 // lanes {0-3,12-15,20-27} together: two lane groups whose taps sit in one row differ by one pixel and never collide; the
 // pairs that straddle rows (taps 2|3) need the row stride to be 2 pixels mod 16 -> 50 pixels.
 #include "ac_common.h"
-#include <stdlib.h>
 
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -24,94 +23,49 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define W9_TH 8
 #define W9_PH (W9_TH + 2)
 #define W9_CB 8                  // input channels per stage
-// Tile geometry by GX = 16-pixel groups per tile row (two tile rows per wave): 8 x 32 pixels (GX 2: the 96-channel tile and, until round 4,
-// the 48-channel one), 8 x 48 (GX 3) and 8 x 64 (GX 4) for the 48-channel tile - the dual of what the 96-channel tile did for C % 96 == 0:
-// a staged weight byte and an A fragment read feed 1.5x / 2x the MFMAs, the halo falls from 1.56x to 1.46x / 1.41x of the tile.
-template <int GX> struct W9Geo {
-    static constexpr int TW = 16 * GX;                 // tile width in pixels
-    static constexpr int NQ = 2 * GX;                  // 16-pixel groups per wave
+// Tile geometry: 8 x 32 pixels, two 16-pixel groups per tile row and two tile rows per wave, for the 96-channel and the 48-channel tile
+// alike.  Wider 48-channel tiles (8 x 48 and 8 x 64: a staged weight byte and an A fragment read feed 1.5x / 2x the MFMAs, the halo falls
+// from 1.56x to 1.46x / 1.41x of the tile) were built and measured in round 4 and were slower (profiles/r04b); removed, see git history
+// before this commit.
+struct W9Geo {
+    static constexpr int TW = 32;                      // tile width in pixels
+    static constexpr int NQ = 4;                       // 16-pixel groups per wave
     static constexpr int LW = TW + 8;                  // staged columns per patch row: the aligned float4 of a row, x0 - 4 .. x0 + TW + 3
     static constexpr int NQD = LW / 4;                 // float4 per staged row
-    static constexpr int RS = LW + 10;                 // LDS row stride in pixels: 50 / 66 / 82, all 2 (mod 16) - see the bank note above
+    static constexpr int RS = LW + 10;                 // LDS row stride in pixels: 50 = 2 (mod 16) - see the bank note above
     static constexpr int PATCH_BYTES = 2 * W9_PH * RS * W9_CB * 2;
     static constexpr int OUT_STRIDE = TW + 4;
     static constexpr int NR = (2 * W9_PH * NQD + 255) / 256;      // staging rounds: (row, float4, channel quad) slots over 256 threads
-    static constexpr int QH = NQ == 8 ? 4 : NQ;        // B fragments held at once (8 groups x hi/lo would be 64 VGPRs beside the 64 of the carried tap 8)
 };
-#ifndef W9_PROBE
-#define W9_PROBE 0                   // bit mask of ablations for the probe builds of tools/sharing_probe_*.py (never the product):
-#endif                               // 1 weights first in LDS, 2 no LDS-DMA, 4 no MFMA, 8 no activation staging, 0x10 no shared tap-8 step,
-                                     // 0x20 no epilogue, 0x40 no K loop, 0x80 no activation loads, 0x100 weights fetched for stage 0 only (timing probe: what the
-                                     // per-stage weight DMA costs, i.e. what LDS-resident weights could win)
-#ifndef W9_PIPE
-#define W9_PIPE 1                    // software-pipelined fragment reads in the K loop (0: the compiler's schedule, kept for A/B runs)
-#endif
-#ifndef W9_ASM_DMA_ALL
-#define W9_ASM_DMA_ALL 0             // 1: the hidden (inline assembly) weight DMA in the 48-channel / row-exact variants too (A/B switch)
-#endif
-#ifndef W9_PF
-#define W9_PF 1                      // activation-patch prefetch depth of the 48-channel tile in stages.  1: the product.  2 (A/B switch): two register sets and
-#endif                               // LDS-only barriers; 226 VGPRs = two workgroups per CU (-DW9_S8_OCC=2); measured 10 % SLOWER than depth 1 there (profiles/r04x)
-#ifndef W9_S8_OCC
-#define W9_S8_OCC 3                  // workgroups per CU of the 48-channel variant
-#endif
-#ifndef W9_FIRST_OCC
-#define W9_FIRST_OCC 3               // workgroups per CU of the fused first conv
-#endif
 
 // w9_dma16 = ac_lds_dma16 (ac_common.h): the LDS-DMA issued from inline assembly, hidden from the compiler's wait-count pass.
 #define w9_dma16 ac_lds_dma16
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() is a release / acquire fence over ALL address spaces: the compiler puts
-// s_waitcnt vmcnt(0) in front of every s_barrier, so no global load can stay in flight across a stage boundary - a patch prefetch TWO
-// stages ahead (W9_PF 2) would be forced to land one stage early (round 2's depth-2 experiment, profiles/r02g, ran into exactly that).  With
-// this barrier the loads do stay in flight - and the kernel is slower still (profiles/r04x): it is not waiting for its loads.  Global data the
-// kernel reads (patch loads, weight DMA) is waited for by counted s_waitcnt vmcnt where it is consumed; what it writes it never reads.
-__device__ __forceinline__ void w9_barrier() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
-// s_waitcnt vmcnt(N) alone (gfx9 encoding: vmcnt[3:0] | expcnt << 4 | lgkmcnt << 8 | vmcnt[5:4] << 14): vector memory operations return in
-// order, so this waits for everything issued before the N youngest
-template <int N> __device__ __forceinline__ void w9_wait_vm() { __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14)); }
 __device__ inline unsigned short w9_bits(_Float16 h) { return __builtin_bit_cast(unsigned short, h); }
 
-#if W9_PROBE & 4                      // probe build: the operands stay live, the matrix instruction is not issued
-__device__ __forceinline__ f32x4 w9_mfma(f16x8 a, f16x8 b, f32x4 c) { asm volatile("" :: "v"(a), "v"(b)); return c; }
-#else
 __device__ __forceinline__ f32x4 w9_mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-#endif
 
-// MT = 16-row output-channel tiles per workgroup: 6 (96 channels, two workgroups per CU) or 3 (48 channels).  GX: W9Geo.
+// MT = 16-row output-channel tiles per workgroup: 6 (96 channels, two workgroups per CU) or 3 (48 channels).
 // ROWX: the row-exact path of ac_common.h (per-row staging scales, power-of-two fragment factors); s_ex = log2 scale per patch row.
 // FIRST fuses the graph's first 1x1 convolution (C0 <= 4 spectrogram channels -> C_in, + bias + ReLU) into the loader: x is the
 // [B][C0][H][W] spectrogram, a thread's four spectrogram float4 are loaded ONCE and every stage's 8 channels are generated from
 // them per staged pixel (s_first = [C_in][w1[0..3], b1] in LDS; float32 FMAs in ac_conv1x1_small's order, so the values are
 // bit-identical to running that kernel first) - the C_in-channel tensor never touches HBM and the K loop has no activation loads.
-// Every accumulator receives its products in the same order whatever MT / GX (k-step by k-step: ah*bl, al*bh, ah*bh), and the
-// activation scale is a function of the tile's ROWS only, so all geometries produce bit-identical outputs.
-template <int MT, int GX, int EP_M, int PF, bool RELU, bool ROWX, bool FIRST>
+// Every accumulator receives its products in the same order whatever MT (k-step by k-step: ah*bl, al*bh, ah*bh), and the
+// activation scale is a function of the tile's ROWS only, so both tiles produce bit-identical outputs.
+template <int MT, int EP_M, bool RELU, bool ROWX, bool FIRST>
 __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8* __restrict__ wbase /* this channel block's fragments */, const float* __restrict__ bias,
                                         float* __restrict__ out, int C_in, int C_out, int H, int W, float w_unscale,
                                         float* __restrict__ out_amax, unsigned char* s_raw, const int* s_ex, int ex_min,
                                         int co_base, int b, int y0, int x0, const float* s_first, int C0) {
-    using G = W9Geo<GX>;
+    using G = W9Geo;
     constexpr int W9_MT = MT, NQ = G::NQ, RS = G::RS, NR = G::NR;
-    constexpr int QH = G::QH;
-    constexpr bool PIPE = W9_PIPE && MT == 6 && GX == 2 && !ROWX;  // the 48-channel variants have no registers for it (measured on 8 x 32: spills, 40 % slower)
+    constexpr bool PIPE = MT == 6 && !ROWX;                   // software-pipelined fragment reads in the K loop; the 48-channel variants have no registers for it (measured on 8 x 32: spills, 40 % slower)
     constexpr int W9_KFR = 2 * MT * 64;                       // 16-byte fragments per k-step (hi, lo)
-#if W9_PROBE & 1                      // probe build: weight buffers first, so every LDS-DMA lands 1 KiB aligned
-    f16x8* s_w0 = reinterpret_cast<f16x8*>(s_raw);
-    f16x8* s_w1 = s_w0 + 2 * W9_KFR;
-    unsigned short* s_hi = reinterpret_cast<unsigned short*>(s_raw + 5 * W9_KFR * 16);
-    unsigned short* s_lo = s_hi + W9_PH * RS * W9_CB;
-#else
     unsigned short* s_hi = reinterpret_cast<unsigned short*>(s_raw);
     unsigned short* s_lo = s_hi + W9_PH * RS * W9_CB;
     f16x8* s_w0 = reinterpret_cast<f16x8*>(s_raw + G::PATCH_BYTES);           // even stages: 2 k-steps
     f16x8* s_w1 = s_w0 + 2 * W9_KFR;                                           // odd stages: 2 k-steps (+ the shared tap-8 step)
-#endif
     float* s_out = reinterpret_cast<float*>(s_raw);                           // [16 EP_M co][8 rows][TW + 4], MT / EP_M passes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, px = lane & 15;
@@ -165,24 +119,19 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
     for (int q = 0; q < NQ; ++q) { k8h[q] = (f16x8)(_Float16)0; k8l[q] = (f16x8)(_Float16)0; }
 
     // fragments per stage in the packed weights: [cob][cb][3 k-steps][2][MT][64]; the third k-step exists for cb & 3 == 3 only
-    float4 pre_x[PF][NR][4];            // PF register sets: stage cb's patch sits in set cb % PF (static after the unroll by PF below)
+    float4 pre_x[NR][4];                // the patch of the next stage, in flight while this one is multiplied
 
-    auto prefetch_x = [&](int cb, int set) {
+    auto prefetch_x = [&](int cb) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int ci = FIRST ? q : cb * W9_CB + a_c4[r] * 4 + q;            // FIRST: the spectrogram's channels, fetched once
-#if W9_PROBE & 0x80
-                pre_x[set][r][q] = make_float4(1.f + ci, 2.f, 3.f, 4.f);
-#else
-                pre_x[set][r][q] = (!FIRST || q < C0) ? *reinterpret_cast<const float4*>(xb + (size_t)ci * plane + a_ld[r]) : make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
+                pre_x[r][q] = (!FIRST || q < C0) ? *reinterpret_cast<const float4*>(xb + (size_t)ci * plane + a_ld[r]) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
         }
     };
     auto prefetch_w = [&](int cb) {
-        if ((W9_PROBE & 0x100) && cb > 0) return;
         const f16x8* wcb = wbase + (size_t)cb * 3 * W9_KFR;
         f16x8* dst = (cb & 1) ? s_w1 : s_w0;
         const bool third = ((cb & 3) == 3) || cb == n_cb - 1;                       // this stage carries the shared tap-8 k-step
@@ -190,24 +139,16 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
 #pragma unroll
         for (int i = 0; i < 9; ++i) {
             const int inst = wave + 4 * i;
-#if W9_PROBE & 2                      // probe build: no LDS-DMA - the fragments go through registers (slow; an aggressor only)
-            if (inst < n_inst) dst[inst * 64 + lane] = wcb[inst * 64 + lane];
-#else
             if (inst < n_inst) {
-#if W9_ASM_DMA_ALL
-                w9_dma16(wcb + inst * 64 + lane, dst + inst * 64);
-#else
                 if constexpr (PIPE) w9_dma16(wcb + inst * 64 + lane, dst + inst * 64);
                 else __builtin_amdgcn_global_load_lds(wcb + inst * 64 + lane, dst + inst * 64, 16, 0, 0);
-#endif
             }
-#endif
         }
     };
     // split one slot's 4 pixels x 4 channels to f16 hi / lo and store them: two 8-byte stores per pixel
-    auto stage_slot = [&](int cb, int r, int set) {
+    auto stage_slot = [&](int cb, int r) {
         const float zs = a_zs[r];
-        const float* v4[4] = {&pre_x[set][r][0].x, &pre_x[set][r][1].x, &pre_x[set][r][2].x, &pre_x[set][r][3].x};
+        const float* v4[4] = {&pre_x[r][0].x, &pre_x[r][1].x, &pre_x[r][2].x, &pre_x[r][3].x};
         if (FIRST) {
             // two pixels at a time: all sixteen generated values at once cost 2 GB of scratch per launch, one pixel at a time
             // re-reads the 1x1 weights from LDS four times (measured 30 % slower)
@@ -265,27 +206,24 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
     // the ten row maxima arrive) was built and measured in round 4: bit-identical and 14 % SLOWER at C = 48 (3.62 -> 4.14 ms), 2 % at C = 96
     // (profiles/r04i): vmcnt returns in order, so the wait for the (L2-resident) maxima then also waits for the HBM-bound patch loads,
     // and the three workgroups of a CU stop overlapping their prologues with one another's K loops.
-    static_assert(PF == 1 || !FIRST, "the fused first conv fetches its spectrogram patch once per tile");
-    prefetch_w(0); prefetch_x(0, 0);
-    if (PF == 2) prefetch_x(1, 1);       // n_cb >= 2 (C_in % 16 == 0)
-    // In flight at the top of stage cb, oldest first: [PF 2: X(cb), issued two stages ago] W(cb) X(cb + 1).  The compiler waits for X(cb) where
-    // stage_slot reads it (counted: W and X(cb + 1) stay in flight); W(cb) is waited for in front of the stage's second barrier with the
-    // X(cb + 1) loads (4 NR instructions per lane) still out.  n_cb is even, so the loop below is unrolled by PF and the set index is static.
-    for (int cb0 = 0; cb0 < ((W9_PROBE & 0x40) ? 0 : n_cb); cb0 += PF) {
+    prefetch_w(0); prefetch_x(0);
+    // In flight at the top of stage cb, oldest first: W(cb) X(cb + 1).  The compiler waits for X(cb) where stage_slot reads it; W(cb) is waited
+    // for in front of the stage's second barrier.  A prefetch depth of two stages (two register sets, LDS-only barriers and counted vmcnt so
+    // that the loads stay in flight across a stage boundary; 226 VGPRs = two workgroups per CU) was built for the 48-channel tile and measured
+    // in round 4: 10 % SLOWER than depth 1 (profiles/r04x) - the kernel is not waiting for its loads; removed, see git history before this commit.
+    constexpr int PF = 1;                // the loop nest keeps the shape of that build: flattened, the compiler allocates registers differently
+    for (int cb0 = 0; cb0 < n_cb; cb0 += PF) {
 #pragma unroll
     for (int h = 0; h < PF; ++h) {
         const int cb = cb0 + h;
-        if (PF == 2) w9_barrier(); else __syncthreads();      // previous stage fully consumed
-        if (!(W9_PROBE & 8)) {
+        __syncthreads();                 // previous stage fully consumed
 #pragma unroll
-            for (int r = 0; r < NR; ++r)
-                if (a_live[r]) stage_slot(cb, r, h);
-        }
-        // this stage's weight fragments have landed
-        if (PF == 2) { if (cb + 1 < n_cb) w9_wait_vm<4 * NR>(); else w9_wait_vm<0>(); w9_barrier(); }
-        else { __builtin_amdgcn_s_waitcnt(0); __syncthreads(); }
+        for (int r = 0; r < NR; ++r)
+            if (a_live[r]) stage_slot(cb, r);
+        __builtin_amdgcn_s_waitcnt(0);   // this stage's weight fragments have landed
+        __syncthreads();
         if (cb + 1 < n_cb) prefetch_w(cb + 1);
-        if (!FIRST && cb + PF < n_cb) prefetch_x(cb + PF, h);
+        if (!FIRST && cb + 1 < n_cb) prefetch_x(cb + 1);
         const f16x8* s_w = (cb & 1) ? s_w1 : s_w0;
         if constexpr (PIPE) {
         // Fragment reads run AHEAD of the MFMAs that consume them (the compiler's own schedule drained lgkmcnt to 0 in front of every
@@ -293,7 +231,7 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
         // A fragments (2 per unit) are double-buffered and requested one unit ahead; the B fragments of the next k-step replace the
         // current ones pair by pair inside the last unit of a k-step, behind the MFMAs that read them last.  sched_barriers pin the
         // order; the waits are the compiler's counted lgkmcnt(N).
-        const bool third = (((cb & 3) == 3) || cb == n_cb - 1) && !(W9_PROBE & 0x10);
+        const bool third = ((cb & 3) == 3) || cb == n_cb - 1;
         f16x8 bh[4], bl[4], ah[2], al[2];
         auto ld_b = [&](int ks, int q) {
             const int off = b_tap[ks] + ((q >> 1) * RS + (q & 1) * 16) * W9_CB;
@@ -332,7 +270,7 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 } else {
-                    if (last_m && ks == 1 && !(W9_PROBE & 0x10)) {
+                    if (last_m && ks == 1) {
                         // tap 8 (dy = dx = 2) of this stage goes into lane group cb & 3 of the carried fragments; requested in front
                         // of the stage's last unit so that a shared step that follows finds them landed
                         if (g == (cb & 3)) {
@@ -374,42 +312,39 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const int dy = (4 * ks + g) / 3;              // this lane group's tap row (ROWX only)
+            f16x8 bh[NQ], bl[NQ];
 #pragma unroll
-            for (int q0 = 0; q0 < NQ; q0 += QH) {         // QH pixel groups at a time (8 x 64 tile: two halves, A fragments read per half)
-                f16x8 bh[QH], bl[QH];
+            for (int q = 0; q < NQ; ++q) {
+                const int ty = 2 * wave + (q >> 1);
+                const int off = b_tap[ks] + ((q >> 1) * RS + (q & 1) * 16) * W9_CB;        // one address register per k-step, q in the offset field
+                bh[q] = *reinterpret_cast<const f16x8*>(&s_hi[off]);
+                bl[q] = *reinterpret_cast<const f16x8*>(&s_lo[off]);
+                if (ROWX) { const _Float16 f = ac_rowx_frag_factor(s_ex, ty, dy); bh[q] *= (f16x8)f; bl[q] *= (f16x8)f; }
+            }
 #pragma unroll
-                for (int qq = 0; qq < QH; ++qq) {
-                    const int q = q0 + qq, ty = 2 * wave + q / GX;
-                    const int off = b_tap[ks] + ((q / GX) * RS + (q % GX) * 16) * W9_CB;    // one address register per k-step, q in the offset field
-                    bh[qq] = *reinterpret_cast<const f16x8*>(&s_hi[off]);
-                    bl[qq] = *reinterpret_cast<const f16x8*>(&s_lo[off]);
-                    if (ROWX) { const _Float16 f = ac_rowx_frag_factor(s_ex, ty, dy); bh[qq] *= (f16x8)f; bl[qq] *= (f16x8)f; }
-                }
+            for (int m = 0; m < W9_MT; ++m) {
+                const f16x8 ah = s_w[((ks * 2 + 0) * W9_MT + m) * 64 + lane];
+                const f16x8 al = s_w[((ks * 2 + 1) * W9_MT + m) * 64 + lane];
 #pragma unroll
-                for (int m = 0; m < W9_MT; ++m) {
-                    const f16x8 ah = s_w[((ks * 2 + 0) * W9_MT + m) * 64 + lane];
-                    const f16x8 al = s_w[((ks * 2 + 1) * W9_MT + m) * 64 + lane];
-#pragma unroll
-                    for (int qq = 0; qq < QH; ++qq) {
-                        acc[m][q0 + qq] = w9_mfma(ah, bl[qq], acc[m][q0 + qq]);
-                        acc[m][q0 + qq] = w9_mfma(al, bh[qq], acc[m][q0 + qq]);
-                        acc[m][q0 + qq] = w9_mfma(ah, bh[qq], acc[m][q0 + qq]);
-                    }
+                for (int q = 0; q < NQ; ++q) {
+                    acc[m][q] = w9_mfma(ah, bl[q], acc[m][q]);
+                    acc[m][q] = w9_mfma(al, bh[q], acc[m][q]);
+                    acc[m][q] = w9_mfma(ah, bh[q], acc[m][q]);
                 }
             }
         }
         // tap 8 (dy = dx = 2) of this stage goes into lane group cb & 3 of the carried fragments
-        if (g == (cb & 3) && !(W9_PROBE & 0x10)) {
+        if (g == (cb & 3)) {
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const int ty = 2 * wave + q / GX;
-                const int off = b_lane + ((2 + q / GX) * RS + 2 + (q % GX) * 16) * W9_CB;
+                const int ty = 2 * wave + (q >> 1);
+                const int off = b_lane + ((2 + (q >> 1)) * RS + 2 + (q & 1) * 16) * W9_CB;
                 k8h[q] = *reinterpret_cast<const f16x8*>(&s_hi[off]);
                 k8l[q] = *reinterpret_cast<const f16x8*>(&s_lo[off]);
                 if (ROWX) { const _Float16 f = ac_rowx_frag_factor(s_ex, ty, 2); k8h[q] *= (f16x8)f; k8l[q] *= (f16x8)f; }
             }
         }
-        if (((cb & 3) == 3 || cb == n_cb - 1) && !(W9_PROBE & 0x10)) {           // a trailing group of two stages: lane groups 2-3 meet zero weights
+        if ((cb & 3) == 3 || cb == n_cb - 1) {           // a trailing group of two stages: lane groups 2-3 meet zero weights
 #pragma unroll
             for (int m = 0; m < W9_MT; ++m) {
                 const f16x8 ah = s_w[((2 * 2 + 0) * W9_MT + m) * 64 + lane];
@@ -426,11 +361,7 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
     }
     }
     // ---- epilogue in passes of EP_M row tiles through the LDS tile [co][row][x] -> whole row segments of the tile per store
-    float vmax[2] = {0.f, 0.f};          // this wave's two output rows (ty = 2 wave + q / GX)
-#if W9_PROBE & 0x20
-    if (acc[0][0][0] == 12345.678f) out[0] = acc[0][0][0] + acc[W9_MT - 1][NQ - 1][3];      // probe build: no epilogue (the accumulators stay live)
-    return;
-#endif
+    float vmax[2] = {0.f, 0.f};          // this wave's two output rows (ty = 2 wave + q / 2)
 #pragma unroll
     for (int m0 = 0; m0 < W9_MT; m0 += EP_M) {
         const int n_m = (W9_MT - m0) < EP_M ? (W9_MT - m0) : EP_M;
@@ -441,14 +372,14 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
                 const int m = m0 + mm;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
-                    const int ty = 2 * wave + q / GX, tx = (q % GX) * 16 + px;
+                    const int ty = 2 * wave + (q >> 1), tx = (q & 1) * 16 + px;
                     const float us = ROWX ? w_unscale * ac_rowx_unscale(s_ex, ty) : unscale;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int co = mm * 16 + g * 4 + r;
                         float v = acc[m][q][r] * us + bias[co_base + m0 * 16 + co];
                         if (RELU) v = fmaxf(v, 0.f);
-                        vmax[q / GX] = fmaxf(vmax[q / GX], fabsf(v));
+                        vmax[q >> 1] = fmaxf(vmax[q >> 1], fabsf(v));
                         s_out[(co * W9_TH + ty) * G::OUT_STRIDE + tx] = v;
                     }
                 }
@@ -470,18 +401,17 @@ __device__ __forceinline__ void w9_tile(const float* __restrict__ x, const f16x8
     }
 }
 
-template <int MT, int GX, int OCC, bool RELU, bool FIRST>
+template <int MT, int OCC, bool RELU, bool FIRST>
 __global__ __launch_bounds__(256, OCC) void k_conv3x3_f16x3_w96(const float* __restrict__ x, const f16x8* __restrict__ wpk,
                                                               const float* __restrict__ bias, float* __restrict__ out,
                                                               int C_in, int C_out, int H, int W, float w_unscale, int bw,
                                                               const float* __restrict__ in_amax, float* __restrict__ out_amax,
                                                               const float* __restrict__ w1, const float* __restrict__ b1, int C0,
                                                               float amax_gain, float amax_offs) {
-    using G = W9Geo<GX>;
+    using G = W9Geo;
     constexpr int W9_COB = 16 * MT, W9_KFR = 2 * MT * 64;
     // row tiles per epilogue pass: the output tile [16 EP_M][8][TW + 4] must fit the workgroup's share of the LDS (160 KB / OCC)
-    constexpr int EP_M = (MT == 6) ? 3 : (GX == 3 ? 3 : 2);
-    constexpr int PF = (MT == 3 && !FIRST) ? W9_PF : 1;        // the 96-channel tile has no registers for a second set (252 of 256), the first conv no per-stage loads
+    constexpr int EP_M = (MT == 6) ? 3 : 2;
     constexpr int EP_BYTES = EP_M * 16 * W9_TH * G::OUT_STRIDE * 4;
     constexpr int K_BYTES = G::PATCH_BYTES + (2 + 3) * W9_KFR * 16;
     static_assert((K_BYTES > EP_BYTES ? K_BYTES : EP_BYTES) * OCC <= 160 * 1024 - OCC * 2048, "LDS per CU");
@@ -528,17 +458,10 @@ __global__ __launch_bounds__(256, OCC) void k_conv3x3_f16x3_w96(const float* __r
     ex_min = __builtin_amdgcn_readfirstlane(ex_min);
     ex_max = __builtin_amdgcn_readfirstlane(ex_max);
     if (ex_min != AC_EX_NONE && ex_max - ex_min > AC_ROWX_SPREAD)
-        w9_tile<MT, GX, EP_M, PF, RELU, true, FIRST>(x, wpk + (size_t)cob * (C_in / W9_CB) * 3 * W9_KFR, bias, out, C_in, C_out, H, W, w_unscale, out_amax, s_raw, s_ex, ex_min, cob * W9_COB, b, y0, x0, s_first, C0);
+        w9_tile<MT, EP_M, RELU, true, FIRST>(x, wpk + (size_t)cob * (C_in / W9_CB) * 3 * W9_KFR, bias, out, C_in, C_out, H, W, w_unscale, out_amax, s_raw, s_ex, ex_min, cob * W9_COB, b, y0, x0, s_first, C0);
     else
-        w9_tile<MT, GX, EP_M, PF, RELU, false, FIRST>(x, wpk + (size_t)cob * (C_in / W9_CB) * 3 * W9_KFR, bias, out, C_in, C_out, H, W, w_unscale, out_amax, s_raw, s_ex, ex_min, cob * W9_COB, b, y0, x0, s_first, C0);
+        w9_tile<MT, EP_M, RELU, false, FIRST>(x, wpk + (size_t)cob * (C_in / W9_CB) * 3 * W9_KFR, bias, out, C_in, C_out, H, W, w_unscale, out_amax, s_raw, s_ex, ex_min, cob * W9_COB, b, y0, x0, s_first, C0);
 }
-
-#ifndef AC_PROBES
-#define AC_PROBES 0                   // 1: the probe build of tools/conv_order_probe.py - tile width and band width taken from the environment,
-#endif                                // and the 8 x 48 / 8 x 64 instantiations of the 48-channel tile compiled in (measured slower: profiles/r04b)
-#if AC_PROBES
-static int w9_env_int(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#endif
 
 // Band width of the work order in tiles: the widest divisor of the tile row that keeps a band within 768 pixels.  A band edge costs two
 // partial 128-byte lines per patch row that no resident workgroup shares, and the L2 fetches whole lines (profiles/r04a: one 16-byte
@@ -558,41 +481,24 @@ static int w9_launch(ac_ctx* ctx, const float* x, const void* w_packed, const fl
     AC_REQUIRE(B > 0 && C_in > 0 && C_in % 16 == 0 && C_out > 0 && C_out % cob_width == 0, "C_in % 16 == 0 and C_out % (96 or 48) == 0");
     AC_REQUIRE(H > 0 && H % W9_TH == 0 && W > 0 && W % 32 == 0, "H % 8 == 0 and W % 32 == 0");
     AC_REQUIRE((long long)H * W < (1LL << 31), "plane too large");
-    int gx = 2;                          // 8 x 32 pixel tiles (W9Geo)
-#if AC_PROBES
-    if (cob_width == 48) {
-        const int want = w9_env_int("AC_PROBE_CONV_GX");
-        if (want == 3 && W % 48 == 0) gx = 3;
-        if (want == 4 && W % 64 == 0) gx = 4;
-    }
-#endif
-    const int tw = 16 * gx;
+    constexpr int tw = W9Geo::TW;
     const long long nblk = (long long)B * (C_out / cob_width) * (H / W9_TH) * (W / tw);
     AC_REQUIRE(nblk < (1LL << 31), "grid too large");
-    const int tiles_x = W / tw;
-    int bw = w9_band_width(tiles_x, tw);
-#if AC_PROBES
-    { const int v = w9_env_int("AC_PROBE_CONV_BW"); if (v > 0 && tiles_x % v == 0) bw = v; }
-#endif
+    const int bw = w9_band_width(W / tw, tw);
     dim3 grid((unsigned)nblk), block(256);
     hipStream_t st = (hipStream_t)stream;
     const f16x8* wp = (const f16x8*)w_packed;
-#define W9_GO(MT_, GX_, OCC_, RELU_, FIRST_) hipLaunchKernelGGL((k_conv3x3_f16x3_w96<MT_, GX_, OCC_, RELU_, FIRST_>), grid, block, 0, st, x, wp, bias, out, \
+    constexpr int OCC48 = 3;             // workgroups per CU of the 48-channel variants (the 96-channel tile: 2, bounded by its LDS)
+#define W9_GO(MT_, OCC_, RELU_, FIRST_) hipLaunchKernelGGL((k_conv3x3_f16x3_w96<MT_, OCC_, RELU_, FIRST_>), grid, block, 0, st, x, wp, bias, out, \
         C_in, C_out, H, W, w_unscale, bw, in_amax, out_amax, w1, b1, C0, amax_gain, amax_offs)
-#define W9_GO_R(MT_, GX_, OCC_, FIRST_) do { if (relu) W9_GO(MT_, GX_, OCC_, true, FIRST_); else W9_GO(MT_, GX_, OCC_, false, FIRST_); } while (0)
+#define W9_GO_R(MT_, OCC_, FIRST_) do { if (relu) W9_GO(MT_, OCC_, true, FIRST_); else W9_GO(MT_, OCC_, false, FIRST_); } while (0)
     if (w1) {
         AC_REQUIRE(b1 && C0 >= 1 && C0 <= 4 && C_in <= 64 && cob_width == 48, "fused first conv: 1 <= C0 <= 4, C_in <= 64, 48-channel workgroups");
-#if AC_PROBES
-        if (gx == 4) W9_GO_R(3, 4, 2, true); else if (gx == 3) W9_GO_R(3, 3, 2, true); else
-#endif
-        W9_GO_R(3, 2, W9_FIRST_OCC, true);
+        W9_GO_R(3, OCC48, true);
     } else if (cob_width == 96) {
-        W9_GO_R(6, 2, 2, false);
+        W9_GO_R(6, 2, false);
     } else {
-#if AC_PROBES
-        if (gx == 4) W9_GO_R(3, 4, 2, false); else if (gx == 3) W9_GO_R(3, 3, 2, false); else
-#endif
-        W9_GO_R(3, 2, W9_S8_OCC, false);
+        W9_GO_R(3, OCC48, false);
     }
 #undef W9_GO_R
 #undef W9_GO

@@ -2,11 +2,13 @@
 compute wrong frames when workgroups of the two share compute units?  (tools/sharing_probe_victims.py part 0 showed that no second
 process is needed: 1637 of 1640 iSTFT launches beside a conv loop on another stream of the SAME process were wrong.)
 
-Aggressors: the product conv (48- and 96-channel workgroups) and ablated builds of it (tools/probes/build_probes.sh, W9_PROBE bits:
-4 no MFMA, 8 no activation staging, 0x10 no shared tap-8 step, 0x20 no epilogue, 0x40 no K loop, 0x80 no activation loads), the TDF
-GEMM as the known-harmless control.  Victims: the product iSTFT, builds of it without twiddle factors / without SLP-packed float
-math / with L1-bypassing loads, and the FFT's LDS traffic as pure data movement (canary.hip).  Every cell = wrong launches / launches
-in ~1.2 s, each launch checked bit for bit against the victim's own solo result."""
+Aggressors: the product conv (48- and 96-channel workgroups), the TDF GEMM as the known-harmless control.  Victims: the product iSTFT
+(built without packed float32), ac_mdx.hip alone built with and without packed float32 and without SLP-packed float math
+(tools/probes/build_probes.sh), and the FFT's LDS traffic as pure data movement (canary.hip).  Every cell = wrong launches / launches
+in ~1.2 s, each launch checked bit for bit against the victim's own solo result.
+The ablated conv aggressors (no MFMA / no staging / no epilogue / no K loop ...) and the iSTFT victims without twiddle factors / with
+L1-bypassing loads that narrowed the finding down (profiles/r03_gpu_sharing_rootcause.log) were compile-time switches of the kernel
+sources up to commit 03dbdf0; they were removed with the switches."""
 import ctypes as C, os, sys, time
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,9 +24,7 @@ PB = f"{ROOT}/tools/probes/build"
 
 def probe_lib(name):
     lib = C.CDLL(f"{PB}/lib{name}.so")
-    for fn in ("ac_conv3x3_f16x3_s8", "ac_conv3x3_f16x3_w96", "ac_mdx_istft"):
-        if hasattr(lib, fn):
-            getattr(lib, fn).restype, getattr(lib, fn).argtypes = _native.SIGNATURES[fn]
+    lib.ac_mdx_istft.restype, lib.ac_mdx_istft.argtypes = _native.SIGNATURES["ac_mdx_istft"]
     return lib
 
 
@@ -47,10 +47,6 @@ wt = torch.randn(384, 3072, generator=gg) / 55; pk, un_l1 = pack_linear(wt.numpy
 sc = torch.ones(48, device=dev); sh = torch.zeros(48, device=dev)
 aggressors = {"none": None, "tdf_l1 (control)": lambda: hip.tdf_linear_f16x3(x48, wp_l1, 384, sc, sh, un_l1),
               "conv48 product": conv_call(hip.lib), "conv96 product": conv_call(hip.lib, True)}
-for bits, what in (("0x04", "no MFMA"), ("0x08", "no activation staging"), ("0x10", "no shared tap-8 step"), ("0x20", "no epilogue"),
-                   ("0x40", "no K loop (prologue + epilogue)"), ("0x80", "no activation loads"), ("0x60", "prologue only"),
-                   ("0x0c", "no MFMA, no staging"), ("0x8c", "no MFMA, no staging, no loads")):
-    aggressors[f"conv48 {what}"] = conv_call(probe_lib(f"conv_p{bits}"))
 
 # ---- victims ---------------------------------------------------------------------------------------------------------------
 NI = 16
@@ -90,8 +86,8 @@ def canary(which, rounds):
 
 
 victims = {}
-for name, fn in (("iSTFT product", istft_with(hip.lib)), ("iSTFT without twiddles", istft_with(probe_lib("mdx_notw"))),
-                 ("iSTFT -fno-slp-vectorize", istft_with(probe_lib("mdx_noslp"))), ("iSTFT nt loads", istft_with(probe_lib("mdx_nt")))):
+for name, fn in (("iSTFT product", istft_with(hip.lib)), ("iSTFT with packed float32", istft_with(probe_lib("mdx_pk"))),
+                 ("iSTFT without packed float32", istft_with(probe_lib("mdx_nopk"))), ("iSTFT -fno-slp-vectorize", istft_with(probe_lib("mdx_noslp")))):
     ref = fn().clone(); torch.cuda.synchronize()
     assert torch.equal(fn(), ref), name
     victims[name] = (lambda fn=fn, ref=ref: (fn() != ref).sum())
@@ -125,11 +121,11 @@ def cell(aggr, victim):
 
 
 only = os.environ.get("ONLY_AGGR", "").split(",") if os.environ.get("ONLY_AGGR") else None
-print("== which ingredient of the conv kernel?  victim = the product iSTFT", flush=True)
+print("== which aggressor?  victim = the iSTFT built with packed float32", flush=True)
 for an, af in aggressors.items():
     if only and not any(o in an for o in only):
         continue
-    bad, n = cell(af, victims["iSTFT product"])
+    bad, n = cell(af, victims["iSTFT with packed float32"])
     print(f"   {an:42s} {bad:5d} / {n:5d} iSTFT launches wrong", flush=True)
 print("== which ingredient of the iSTFT?  aggressor = the product conv (48-channel workgroups)", flush=True)
 for vn, vf in victims.items():

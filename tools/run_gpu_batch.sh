@@ -4,9 +4,6 @@
 # Every step appends to gpurun_out/<tag>.log and stops the batch on its first failure (no GPU step is started after a failed one).
 # Steps:
 #   conv_levels[:lib]   tools/conv_pf_bench.py 32 (optionally on another build of the library, AC_LIB=libaudiocut_hip_<lib>.so)
-#   conv_order | conv_tile   tools/conv_order_probe.py: time per band width (conv_tile: per tile width of the 48-channel tile) and level, then FETCH_SIZE / WRITE_SIZE per variant
-#   conv_ablation:<tags>  tools/conv_ablation.py on the product and on each libaudiocut_hip_<tag>.so (comma-separated W9_PROBE builds)
-#   tdf_order           tools/tdf_order_probe.py on the probe build: time, FETCH_SIZE / WRITE_SIZE per (column blocks, row tiles) super-group
 #   calib               tools/probes/build/fetch_calib under the raw TCC request counters (FETCH_SIZE / WRITE_SIZE calibration)
 #   tdf_levels[:lib]    tools/tdf_tile_bench.py 32
 #   unet_tests[:lib]    tests/test_unet_gpu.py
@@ -35,26 +32,7 @@ for STEP in "$@"; do
   echo "== $STEP" >> $L
   case $NAME in
     conv_levels) AC_LIB=$(libenv $ARG) timeout -k 10 200 python tools/conv_pf_bench.py 32 >> $L 2>&1 || exit 1 ;;
-    conv_ablation) for T in "" ${ARG//,/ }; do AC_LIB=$(libenv $T) timeout -k 10 120 python tools/conv_ablation.py 32 >> $L 2>&1 || exit 1; done ;;
     tdf_levels)  AC_LIB=$(libenv $ARG) timeout -k 10 200 python tools/tdf_tile_bench.py 32 >> $L 2>&1 || exit 1 ;;
-    conv_order|conv_tile)
-      export AC_PROBE_SET=${NAME#conv_} AC_LIB=libaudiocut_hip_probe.so
-      timeout -k 10 400 python tools/conv_order_probe.py 32 >> $L 2>&1 || exit 1
-      for CTR in FETCH_SIZE WRITE_SIZE; do
-        rm -rf $O/pmc_tmp
-        ( cd /tmp && AC_PROBE_PMC=1 timeout -k 10 300 rocprofv3 --pmc $CTR --output-format csv -d $O/pmc_tmp -- python3 $R/tools/conv_order_probe.py 32 > $O/pmc_tmp.log 2>&1 ) || { tail -5 $O/pmc_tmp.log; exit 1; }
-        python3 tools/pmc_by_dispatch.py k_conv3x3_f16x3_w96 $(find $O/pmc_tmp -name "*counter_collection.csv") --seq $O/pmc_tmp.log >> $L 2>&1
-      done
-      rm -rf $O/pmc_tmp ;;
-    tdf_order)
-      export AC_LIB=libaudiocut_hip_probe.so
-      timeout -k 10 400 python tools/tdf_order_probe.py 32 >> $L 2>&1 || exit 1
-      for CTR in FETCH_SIZE WRITE_SIZE; do
-        rm -rf $O/pmc_tmp
-        ( cd /tmp && AC_PROBE_PMC=1 timeout -k 10 300 rocprofv3 --pmc $CTR --output-format csv -d $O/pmc_tmp -- python3 $R/tools/tdf_order_probe.py 32 > $O/pmc_tmp.log 2>&1 ) || { tail -5 $O/pmc_tmp.log; exit 1; }
-        python3 tools/pmc_by_dispatch.py k_tdf_linear_f16x3 $(find $O/pmc_tmp -name "*counter_collection.csv") --seq $O/pmc_tmp.log >> $L 2>&1
-      done
-      rm -rf $O/pmc_tmp ;;
     calib)
       for CTRS in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_BUBBLE_sum TCC_EA0_RD_UNCACHED_32B_sum" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum" "FETCH_SIZE" "WRITE_SIZE" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
         rm -rf $O/pmc_tmp
