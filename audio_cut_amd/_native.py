@@ -59,6 +59,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so final-layer ABI version mismatch")
     if lib.ac_load_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so loader ABI version mismatch")
+    if lib.ac_pack_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so pack ABI version mismatch")
     _lib = lib
     return lib
 
@@ -182,6 +184,20 @@ LOAD_SIGNATURES = {
     "ac_load_abi_version": (C.c_int, []),
     "ac_decode_pcm": (C.c_int, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P, _P]),
 }
+# include/audiocut_hip_pack.h: the export end's sample formats (any of the six WAV subtypes from the resident track or from the iSTFT
+# waves), exported by the same library and versioned on their own
+PACK_SIGNATURES = {
+    "ac_pack_abi_version": (C.c_int, []),
+    "ac_pack_width": (C.c_int, [_I]),
+    "ac_pack_out_align": (C.c_int, [_I]),
+    "ac_pack_pcm": (C.c_int, [_P, _P, _I64, _I, _I64, _I, _P, _P]),
+    "ac_mdx_assemble_pcm": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+}
+# subtype name -> (AC_PACK_* code, bytes per word), and the lookup that refuses every other name: one table for the host conversion,
+# the WAV header and these bindings
+from .utils.audio_export import WAV_SUBTYPES as PACK_SUBTYPES, subtype_info as pack_subtype  # noqa: E402
+
+
 # 4 * AC_PROFILE_BLOCK * AC_PROFILE_MAX_BLOCKS: the samples one step of the largest grid of ac_abs_peak_coverage covers (from
 # twice this many on, every thread of either sweep goes round its loop at least twice)
 PROFILE_GRID_SAMPLES = 4 * 256 * 2048
@@ -199,7 +215,7 @@ def coverage_from(peak: float, count: int, n: int) -> float:
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
                               *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items(),
-                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items()):
+                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items(), *PACK_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -574,6 +590,32 @@ class Context:
         out = torch.empty(3 * n + 3, dtype=torch.uint8, device=self.device)
         _check(self.lib.ac_pack_pcm24(self._h, _ptr(x), n, _ptr(out), _stream()))
         return out[: 3 * n].cpu().numpy()
+
+    def pack_pcm_device(self, x: torch.Tensor, subtype: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A mono [n] or planar stereo [2, n] float32 device track -> its finished sample bytes of `subtype` on the device (uint8
+        [n * channels * width], stereo frames interleaved L, R), one launch of `ac_pack_pcm` (include/audiocut_hip_pack.h).  The
+        rows of a stereo track may be views into wider rows (unit stride along a row, any row stride >= n): nothing is copied.
+        `out`: a uint8 device tensor of at least that many bytes to write into; bytes behind them keep their values."""
+        code, width = pack_subtype(subtype)
+        if x.dtype != torch.float32 or x.device != self.device or x.dim() not in (1, 2) or (x.dim() == 2 and x.shape[0] != 2):
+            raise NativeError("pack_pcm: expected a float32 [n] or [2, n] tensor on the context's device")
+        n, ch = int(x.shape[-1]), x.dim()
+        if n == 0:
+            raise NativeError("pack_pcm: empty track")
+        if x.stride(-1) != 1 or (ch == 2 and x.stride(0) < n):
+            raise NativeError("pack_pcm: the samples of a row must be contiguous and the rows must not overlap")
+        n_bytes = n * ch * width
+        if out is None:
+            out = torch.empty(n_bytes, dtype=torch.uint8, device=self.device)
+        elif out.dtype != torch.uint8 or out.device != self.device or out.dim() != 1 or out.numel() < n_bytes or not out.is_contiguous():
+            raise NativeError(f"pack_pcm: `out` must be a contiguous uint8 tensor of at least {n_bytes} bytes on the context's device")
+        _check(self.lib.ac_pack_pcm(self._h, x.data_ptr(), n, ch, int(x.stride(0)) if ch == 2 else n, code, out.data_ptr(), _stream()))
+        return out[:n_bytes]
+
+    def pack_pcm(self, x: torch.Tensor, subtype: str) -> np.ndarray:
+        """`pack_pcm_device` and one download: the host uint8 array of the track's sample bytes, `pcm_bytes_host(x, subtype)` (of the
+        transposed track for a stereo one) bit for bit."""
+        return self.pack_pcm_device(x, subtype).cpu().numpy()
 
     def decode_pcm(self, raw_dev: torch.Tensor, info, layout: int, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, int]:
         """The sample bytes of a WAV file, resident as a uint8 tensor of at least `info.data_bytes` bytes, -> (track, nonfinite):
@@ -1048,6 +1090,26 @@ class Context:
         _check(self.lib.ac_mdx_assemble_pcm24(self._h, _ptr(track), n, ch, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len), _ptr(eff_start),
                                               _ptr(eff_end), _ptr(item_base), chunk_start.numel(), _ptr(stem), _ptr(rest), _ptr(partials),
                                               parts, _stream()))
+        return stem, rest, partials
+
+    def mdx_assemble_pcm(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base, subtype: str):
+        """`mdx_assemble_pcm24` with the word of `subtype` (one of the six of `PACK_SUBTYPES`): -> (stem, rest, partials), the two
+        streams as uint8 [n * channels * width] on the device - `pack_pcm` of the stems `mdx_assemble_ola` gives, with no float
+        stem in between - and the same float64 [3, parts] partial sums.  One launch (`ac_mdx_assemble_pcm`)."""
+        code, width = pack_subtype(subtype)
+        stereo = self._chk_track(track)
+        n = int(track.shape[-1])
+        if n == 0:
+            raise NativeError("mdx_assemble_pcm: empty track")
+        ch = 2 if stereo else 1
+        groups = -(-n * ch // 4)
+        parts = min(self.ASSEMBLE_PCM24_MAX_PARTIALS, -(-groups // 256))
+        stem = torch.empty(width * ch * n, dtype=torch.uint8, device=self.device)
+        rest = torch.empty(width * ch * n, dtype=torch.uint8, device=self.device)
+        partials = torch.empty((3, parts), dtype=torch.float64, device=self.device)
+        _check(self.lib.ac_mdx_assemble_pcm(self._h, _ptr(track), n, ch, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len), _ptr(eff_start),
+                                            _ptr(eff_end), _ptr(item_base), chunk_start.numel(), code, _ptr(stem), _ptr(rest),
+                                            _ptr(partials), parts, _stream()))
         return stem, rest, partials
 
     # -- U-Net layers (NCHW float32; `in_amax` / `out_amax`: per-item max |x| of the input / output tensor, include/audiocut_hip.h) --

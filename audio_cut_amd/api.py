@@ -23,7 +23,7 @@ channel mean is `librosa.load(mono=True)`'s; a float file holding a NaN or an in
 `audio.sample_rate` is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
-`<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all PCM_24 packed on the GPU (`ac_pack_pcm24`).
+`<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all of the subtype `output.wav.subtype` names (default PCM_24), packed on the GPU (`ac_pack_pcm24`, `ac_pack_pcm`).
 Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included, and the lyrics attachment to segments where an alignment
 ran.  `separate_and_segment` returns the manifest like the reference's does.
 
@@ -188,18 +188,20 @@ def _vocal_separation_plan(export_types: Optional[Sequence[str]]) -> set:
 def _export_vocal_separation(res: Mapping[str, Any], in_path: Path, out_dir: Path, export_types: Optional[Sequence[str]], sr: int,
                              t_start: float) -> Dict[str, Any]:
     """The export half of `_process_vocal_separation_only` (`seamless_splitter.py:975-1036`): `<name>_vocal_<seconds:.1f>.wav` and
-    `<name>_instrumental_<seconds:.1f>.wav` from the PCM_24 bytes the separation produced, and the reference's result dict."""
+    `<name>_instrumental_<seconds:.1f>.wav` from the sample bytes the separation produced, and the reference's result dict.  The
+    bytes are of the subtype `separate_only` read from `output.wav.subtype` and recorded next to them (absent: PCM_24)."""
     import time
     from .utils.audio_export import PackedTrack, SegmentExporter
     plan = _vocal_separation_plan(export_types)
     pcm = res["stem_pcm24"]
+    subtype = pcm.get("subtype", "PCM_24")
     seconds = int(pcm["n"]) / float(sr)
     exporter = SegmentExporter(sr)
     files: Dict[str, Optional[str]] = {"vocal": None, "instrumental": None}
     saved = []
     for kind in ("vocal", "instrumental"):
         if f"full_{kind}" in plan and pcm.get(kind) is not None:      # no instrumental: the reference logs it and goes on (`:1007-1008`)
-            track = PackedTrack.from_pcm24(pcm[kind], int(pcm["n"]), int(pcm["channels"]), sr)
+            track = PackedTrack.from_bytes(pcm[kind], int(pcm["n"]), int(pcm["channels"]), sr, subtype)
             files[kind] = exporter.export_full_track(track, out_dir / f"{in_path.stem}_{kind}_{seconds:.1f}")
             saved.append(files[kind])
     out: Dict[str, Any] = {
@@ -286,8 +288,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     split, export, and the result dict `_build_manifest` reads.  `channels == 2`: the planar stereo track is split (true-stereo
     separation, detection on its channel mean) and every file is written with both channels."""
     import time
-    from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter
+    from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter, configured_subtype
     t_start = time.time()
+    subtype = configured_subtype()          # `output.format` / `output.wav.subtype`: refused here, before any work, if not written
     splitter = SeamlessSplitter(sample_rate=sr, device=device)
     hip = splitter._context()
     audio_dev = None
@@ -343,12 +346,12 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     st = "_stereo" if channels == 2 else ""
     mix_dev = state.get("mix_stereo", audio_dev) if channels == 2 else state.get("mix", audio_dev)
     if "mix_segments" in plan:
-        mix_pk = PackedTrack(audio, sr, hip=hip, dev=mix_dev)
+        mix_pk = PackedTrack(audio, sr, subtype, hip=hip, dev=mix_dev)
         exp.mix_segment_files = exporter.export_spans(mix_pk, spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap,
                                                       **naming)
         exp.saved_files += exp.mix_segment_files
     vocal = res.get("vocal_track" + st)
-    voc_pk = PackedTrack(vocal, sr, hip=hip, dev=state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
+    voc_pk = PackedTrack(vocal, sr, subtype, hip=hip, dev=state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
     if "vocal_segments" in plan and voc_pk is not None:
         exp.vocal_segment_files = exporter.export_spans(voc_pk, spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
                                                         file_suffix="_vocal", duration_map=dmap, **naming)
@@ -358,7 +361,7 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         exp.saved_files.append(exp.full_vocal_file)
     inst = res.get("instrumental_track" + st)
     if "full_instrumental" in plan and inst is not None:
-        inst_pk = PackedTrack(inst, sr, hip=hip, dev=state.get("instrumental" + st))
+        inst_pk = PackedTrack(inst, sr, subtype, hip=hip, dev=state.get("instrumental" + st))
         exp.full_instrumental_file = exporter.export_full_track(inst_pk, out_dir / f"{in_path.stem}_{mode}_instrumental_{np.shape(inst)[-1] / float(sr):.1f}")
         exp.saved_files.append(exp.full_instrumental_file)
     out: Dict[str, Any] = {

@@ -20,6 +20,8 @@ DEFAULTS: Dict[str, Any] = {
                   "target_duration_s": [5.0, 12.0], "lyrics": "auto"},
     # `gpu_decode`: .wav input is decoded on the device from the file's own bytes (`api.load_audio_device`); false: on the host
     "audio": {"sample_rate": 44100, "channels": 1, "gpu_decode": True},
+    # the export format (`unified.yaml:49-51`): `wav` alone is written here; subtype: PCM_U8, PCM_16, PCM_24, PCM_32, FLOAT or DOUBLE
+    "output": {"format": "wav", "wav": {"subtype": "PCM_24"}},
     "gpu_pipeline": {
         "enable": True, "prefer_device": "cuda", "strict_gpu": False,
         "chunk_seconds": 10.0, "overlap_seconds": 2.5, "halo_seconds": 0.5, "align_hop": 4096,

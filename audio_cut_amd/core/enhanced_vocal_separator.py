@@ -60,7 +60,7 @@ class SeparationResult:
     vocal_track_stereo: Optional[np.ndarray] = None
     instrumental_track_stereo: Optional[np.ndarray] = None
     # extension, `separate_only`: {"vocal": uint8 PCM_24 bytes, "instrumental": the same or None, "channels": 1 | 2, "n": N};
-    # stereo frames are interleaved L, R as `PackedTrack` lays them out
+    # stereo frames are interleaved L, R as `PackedTrack` lays them out; "subtype": what the bytes are (absent: PCM_24)
     stem_pcm24: Optional[Dict[str, object]] = None
 
 
@@ -339,9 +339,10 @@ class EnhancedVocalSeparator:
     def separate_only(self, audio: np.ndarray, *, gpu_context: Optional[PipelineContext] = None,
                       audio_dev: Optional[torch.Tensor] = None) -> SeparationResult:
         """Mode `vocal_separation` (reference `seamless_splitter.py:958-1036`): the separation of `separate_for_detection` and
-        nothing of what detection needs.  The iSTFT output goes straight to 24-bit PCM (`ac_mdx_assemble_pcm24`): the result
-        carries `stem_pcm24` and the confidence, no float stems, no feature cache, no VAD segments, no markers.  `audio` is a mono
-        [N] or a planar stereo [2, N] float32 track; a stereo track gives two-channel stems."""
+        nothing of what detection needs.  The iSTFT output goes straight to finished sample bytes of the configured subtype
+        (`output.wav.subtype`; `ac_mdx_assemble_pcm24` for the default PCM_24, `ac_mdx_assemble_pcm` for the other five): the result
+        carries them as `stem_pcm24` (with their `subtype`) and the confidence, no float stems, no feature cache, no VAD segments,
+        no markers.  `audio` is a mono [N] or a planar stereo [2, N] float32 track; a stereo track gives two-channel stems."""
         backend = self._primary_backend
         if backend is None:
             raise RuntimeError("separator backend not initialised")
@@ -378,7 +379,9 @@ class EnhancedVocalSeparator:
         torch.cuda.current_stream(hip.device).synchronize()
         h2d_ms = (time.perf_counter() - t0) * 1000.0
 
-        sep = backend.separate_track(track_dev, sr, gpu_context.plans, timings, defer_sync=True, export_pcm24=True)
+        from ..utils.audio_export import configured_subtype
+        subtype = configured_subtype()
+        sep = backend.separate_track(track_dev, sr, gpu_context.plans, timings, defer_sync=True, export_pcm24=True, export_subtype=subtype)
         t1 = time.perf_counter()
         vocal_h = torch.empty(sep.vocal.shape, dtype=torch.uint8, pin_memory=True)
         inst_h = torch.empty(sep.instrumental.shape, dtype=torch.uint8, pin_memory=True)
@@ -402,7 +405,8 @@ class EnhancedVocalSeparator:
         gm["gpu_pipeline_chunk_invocations"] = len(sep.chunk_ranges)
         gm["mdx23_output_type"] = backend.get_output_type()
         gm["gpu_pipeline_stage_ms"] = dict(timings)
-        pcm = {"vocal": vocal_h.numpy(), "instrumental": inst_h.numpy() if has_inst else None, "channels": 2 if stereo else 1, "n": total}
+        pcm = {"vocal": vocal_h.numpy(), "instrumental": inst_h.numpy() if has_inst else None, "channels": 2 if stereo else 1, "n": total,
+               "subtype": subtype}
         return pcm, confidence
 
     def _side_stream(self, hip) -> "torch.cuda.Stream":

@@ -241,3 +241,12 @@ __device__ inline int pcm16(float v) {
     if (!(s == s)) return 0;
     return ((int)rintf(s)) >> 16;                        // lrintf (half to even), then the two high bytes
 }
+
+// ---- float32 -> 32-bit PCM word (ac_pack_pcm, ac_mdx_assemble_pcm): libsndfile pcm.c f2lei_clip_array, the whole saturated word ----
+__device__ inline int pcm32(float v) {
+    const float s = v * 2147483648.0f;
+    if (s >= 2147483647.0f) return 2147483647;
+    if (s <= -2147483648.0f) return -2147483647 - 1;
+    if (!(s == s)) return 0;
+    return (int)rintf(s);                                // |s| < 2^31 here: the conversion is exact
+}

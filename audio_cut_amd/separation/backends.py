@@ -85,10 +85,11 @@ class TrackSeparation:
 
 @dataclass
 class TrackStemsPcm24:
-    """Device-resident result of `MDX23HipBackend.separate_track(export_pcm24=True)`: the stems as finished PCM_24 bytes."""
+    """Device-resident result of `MDX23HipBackend.separate_track(export_pcm24=True)`: the stems as finished sample bytes, PCM_24
+    or the `export_subtype` asked for (width = its bytes per word)."""
 
-    vocal: torch.Tensor            # uint8 [3 * channels * n]; stereo frames interleaved L, R
-    instrumental: torch.Tensor     # uint8 [3 * channels * n]
+    vocal: torch.Tensor            # uint8 [width * channels * n]; stereo frames interleaved L, R
+    instrumental: torch.Tensor     # uint8 [width * channels * n]
     energy_partials: torch.Tensor  # float64 [3, parts]: partial sums of squares of the mono vocal, mono instrumental, mono mix
     channels: int
     n: int
@@ -198,7 +199,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
     # -- batched fast path ------------------------------------------------------------------------
     def separate_track(self, track_dev: torch.Tensor, sr: int, plans: Sequence[ChunkPlan],
                        timings: Optional[Dict[str, float]] = None, defer_sync: bool = False, before_launch=None,
-                       unet_stream=None, after_launch=None, export_pcm24: bool = False):
+                       unet_stream=None, after_launch=None, export_pcm24: bool = False, export_subtype: str = "PCM_24"):
         """All chunks of a resident track: STFT -> U-Net -> iSTFT -> stem assembly + OLA, no host bounce.
         Everything is queued on the current stream without a host synchronisation; `defer_sync=True` returns at once
         (the caller overlaps host work and calls `result.finish()` later), otherwise the timings are read before returning.
@@ -210,7 +211,8 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         everything is queued (the pipeline's gate only has to keep two tracks' launches from interleaving).
         `track_dev` is a mono [N] or a planar stereo [2, N] float32 track; a stereo one also fills `vocal_stereo` / `instrumental_stereo`.
         `export_pcm24=True` (mode `vocal_separation`): the iSTFT output goes through `ac_mdx_assemble_pcm24` instead of the stem
-        assembly and the per-chunk vocals, and a `TrackStemsPcm24` comes back: no float stem is written.  Not with `unet_stream`."""
+        assembly and the per-chunk vocals, and a `TrackStemsPcm24` comes back: no float stem is written.  Not with `unet_stream`.
+        `export_subtype`: the word of those bytes; another than PCM_24 goes through `ac_mdx_assemble_pcm`."""
         if export_pcm24 and unet_stream is not None:
             raise ValueError("export_pcm24 tracks are separated one at a time (no U-Net stream)")
         hip = self.hip
@@ -260,7 +262,8 @@ class MDX23HipBackend(IVocalSeparatorBackend):
                 t.record_stream(unet_stream)
         with (torch.cuda.stream(unet_stream) if unet_stream is not None else contextlib.nullcontext()):
             sep_out = self._queue_separation(track_dev, n_items, step, timings, ranges, offsets,
-                                             (d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets), export_pcm24)
+                                             (d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets), export_pcm24,
+                                             export_subtype)
             if unet_stream is not None:
                 queued = torch.cuda.Event()
                 queued.record()
@@ -297,7 +300,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         return TrackSeparation(vocal, inst, chunk_vocal, [int(o) for o in offsets[:-1]], ranges, n_items,
                                finish if defer_sync else None, vocal_st, inst_st)
 
-    def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables, export_pcm24=False):
+    def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables, export_pcm24=False, export_subtype="PCM_24"):
         """Queues STFT -> U-Net -> iSTFT of every sub-batch and the stem assembly on the CURRENT stream; no host synchronisation.
         `export_pcm24`: the assembly is `ac_mdx_assemble_pcm24` and the result (vocal bytes, instrumental bytes, partials, events)."""
         hip = self.hip
@@ -321,7 +324,11 @@ class MDX23HipBackend(IVocalSeparatorBackend):
                 ev[3].record()
                 events.append(ev)
         if export_pcm24:        # an instrumental-type network: the two streams, and the first two rows of the partials, change places
-            stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm24(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
+            if export_subtype == "PCM_24":
+                stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm24(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
+            else:
+                stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base,
+                                                                    export_subtype)
             if self.get_output_type() == "vocal":
                 return stem_pcm, rest_pcm, partials, events
             return rest_pcm, stem_pcm, partials[[1, 0, 2]], events

@@ -1,13 +1,17 @@
 """Audio export — mirror of the reference's `src/vocal_smart_splitter/utils/audio_export.py` (`ensure_supported_format`,
 `build_export_options`, `export_audio`) and `core/utils/segment_exporter.py` (`ExportResult`, `SegmentExporter`) for the
-formats this build writes: WAV PCM_24 (the reference default, `audio_export.py:109-111`) and PCM_16.  SURVEY.md §8(f) row 4.
+formats this build writes: WAV of the subtypes PCM_24 (the reference default, `audio_export.py:109-111`), PCM_U8, PCM_16, PCM_32,
+FLOAT and DOUBLE (`output.wav.subtype`, what `soundfile.write(.., subtype=..)` gets there).  SURVEY.md §8(f) row 4.
 
-The float -> integer conversion runs on the GPU (`ac_pack_pcm24`) on the whole resident track once and is libsndfile's
+The float -> integer conversion runs on the GPU (`ac_pack_pcm24`, `ac_pack_pcm`) on the whole resident track once and is libsndfile's
 clipping conversion - python-soundfile sets SFC_SET_CLIPPING on every file, so `soundfile.write` goes through pcm.c
-`f2let_clip_array`: `lrintf(x * 2^31) >> 8`, saturating at 0x7FFFFF / 0x800000 (`>> 16` for PCM_16); segment files are byte slices of that buffer behind a 44-byte RIFF header.  MP3 needs
-pydub + FFmpeg in the reference (`:114-135`) and is refused here.
+`f2let_clip_array`: `lrintf(x * 2^31) >> 8`, saturating at 0x7FFFFF / 0x800000 (`>> 16` for PCM_16, `>> 24` plus 128 for PCM_U8, the
+whole word for PCM_32); FLOAT is the float32 bits as they are and DOUBLE their exact widening, nothing clipped.  Segment files are
+byte slices of that buffer behind a RIFF header (44 bytes for the integer subtypes, 56 with the `fact` chunk of the float ones).
+MP3 needs pydub + FFmpeg in the reference (`:114-135`) and is refused here.
 Stereo tracks are planar (2, N) arrays (the reference writes `(channels, samples)` arrays as multichannel files, `:93-106`): they
-are interleaved frame by frame ([N, 2], on the device before the same packing kernel) and the header carries two channels.
+are interleaved frame by frame (in the packing kernel; PCM_24 as [N, 2] on the device before `ac_pack_pcm24`) and the header
+carries two channels.
 """
 from __future__ import annotations
 
@@ -19,6 +23,19 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 _DEFAULTS: Dict[str, Dict[str, object]] = {"wav": {"subtype": "PCM_24"}}
+
+
+# subtype -> (AC_PACK_* code of include/audiocut_hip_pack.h, bytes per word)
+WAV_SUBTYPES: Dict[str, Tuple[int, int]] = {"PCM_U8": (0, 1), "PCM_16": (1, 2), "PCM_24": (2, 3), "PCM_32": (3, 4), "FLOAT": (4, 4),
+                                            "DOUBLE": (5, 8)}
+
+
+def subtype_info(subtype) -> Tuple[int, int]:
+    """(kernel code, bytes per word) of a subtype name.  Every other name (ULAW, ALAW, the ADPCMs, PCM_S8, a misspelling) is refused."""
+    info = WAV_SUBTYPES.get(subtype) if isinstance(subtype, str) else None
+    if info is None:
+        raise ValueError(f"unsupported WAV subtype {subtype!r}: this build writes {', '.join(WAV_SUBTYPES)}")
+    return info
 
 
 def ensure_supported_format(name: Optional[str]) -> str:
@@ -36,16 +53,43 @@ def build_export_options(format_name: str, *overrides: Optional[Dict[str, object
     return opts
 
 
+def configured_subtype() -> str:
+    """The WAV subtype the configuration asks for: `output.format` (refused unless this build writes it) and `output.<format>`
+    over the format's defaults, as the reference's splitter reads them (`seamless_splitter.py:98-103,167-192`)."""
+    from ..config import get_config
+    fmt = ensure_supported_format(get_config("output.format", "wav"))
+    subtype = build_export_options(fmt, get_config(f"output.{fmt}", {}) or {}).get("subtype", "PCM_24")
+    subtype_info(subtype)
+    return str(subtype)
+
+
 def _export_path(base_path: Path, ext: str) -> Path:
     """`export_audio` (`:70-90`): a base name that already contains a dot keeps it (durations like `_12.3`)."""
     base_path = Path(base_path)
     return base_path.parent / f"{base_path.name}.{ext}" if base_path.suffix else base_path.with_suffix(f".{ext}")
 
 
-def wav_header(n_frames: int, sample_rate: int, channels: int, bytes_per_sample: int) -> bytes:
+def wav_header(n_frames: int, sample_rate: int, channels: int, bytes_per_sample: int, subtype: Optional[str] = None) -> bytes:
+    """Everything in front of the sample bytes.  Integer subtypes (`subtype` None: the integer one of that width): format tag 1,
+    a 16-byte `fmt ` chunk, `data` - 44 bytes.  FLOAT and DOUBLE: tag 3, the same `fmt ` chunk, a `fact` chunk with the frame count,
+    `data` - 56 bytes; no PEAK chunk (libsndfile's carries a timestamp).  A PCM_U8 data chunk of odd length is followed by one pad
+    byte (`wav_pad`), which the RIFF size counts; PCM_24 files keep the layout they have always had here (no pad byte behind an
+    odd number of mono samples), byte for byte, and no other subtype can be odd.  Sizes that do not fit the 32-bit fields are refused: RF64 is not written."""
+    if subtype is not None and subtype_info(subtype)[1] != bytes_per_sample:
+        raise ValueError(f"a {subtype} word has {subtype_info(subtype)[1]} bytes, not {bytes_per_sample}")
+    is_float = subtype in ("FLOAT", "DOUBLE")
     data = n_frames * channels * bytes_per_sample
-    return (b"RIFF" + struct.pack("<I", 36 + data) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 1, channels, sample_rate,
-            sample_rate * channels * bytes_per_sample, channels * bytes_per_sample, 8 * bytes_per_sample) + b"data" + struct.pack("<I", data))
+    riff = (48 if is_float else 36) + data + len(wav_pad(n_frames, channels, bytes_per_sample))
+    if data > 0xFFFFFFFF or riff > 0xFFFFFFFF:
+        raise ValueError(f"{data} sample bytes do not fit a RIFF/WAVE file (32-bit sizes); RF64 is not written")
+    fact = b"fact" + struct.pack("<II", 4, n_frames) if is_float else b""
+    return (b"RIFF" + struct.pack("<I", riff) + b"WAVE" + b"fmt " + struct.pack("<IHHIIHH", 16, 3 if is_float else 1, channels, sample_rate,
+            sample_rate * channels * bytes_per_sample, channels * bytes_per_sample, 8 * bytes_per_sample) + fact + b"data" + struct.pack("<I", data))
+
+
+def wav_pad(n_frames: int, channels: int, bytes_per_sample: int) -> bytes:
+    """The RIFF pad byte behind a PCM_U8 data chunk of odd length, else nothing (see `wav_header` for PCM_24)."""
+    return b"\0" if bytes_per_sample == 1 and (n_frames * channels) & 1 else b""
 
 
 def _sndfile_clip_int32(x: np.ndarray) -> np.ndarray:
@@ -58,9 +102,19 @@ def _sndfile_clip_int32(x: np.ndarray) -> np.ndarray:
 
 
 def pcm_bytes_host(audio: np.ndarray, subtype: str) -> Tuple[np.ndarray, int]:
-    """Host conversion for arrays that never were on the device (tests, tiny inputs): same arithmetic as the kernel, which is
-    libsndfile's clipping float -> PCM conversion: `lrintf(x * 2^31) >> 16` (PCM_16) / `>> 8` (PCM_24)."""
+    """Host conversion for arrays that never were on the device (tests, tiny inputs): same arithmetic as the kernels, which is
+    libsndfile's clipping float -> PCM conversion: `lrintf(x * 2^31)` (PCM_32), `>> 8` (PCM_24), `>> 16` (PCM_16), `(>> 24) + 128`
+    (PCM_U8); FLOAT is the float32 bits as they are (NaN and infinities kept) and DOUBLE their exact widening."""
+    subtype_info(subtype)
     x = np.asarray(audio, dtype=np.float32).reshape(-1)
+    if subtype == "FLOAT":
+        return x.astype("<f4").view(np.uint8), 4
+    if subtype == "DOUBLE":
+        return x.astype("<f8").view(np.uint8), 8
+    if subtype == "PCM_32":
+        return _sndfile_clip_int32(x).astype("<i4").view(np.uint8), 4
+    if subtype == "PCM_U8":
+        return ((_sndfile_clip_int32(x) >> 24) + 128).astype(np.uint8), 1
     if subtype == "PCM_16":
         return (_sndfile_clip_int32(x) >> 16).astype("<i2").view(np.uint8), 2
     v = (_sndfile_clip_int32(x) >> 8).astype(np.int32)
@@ -81,9 +135,10 @@ def _channels_of(audio) -> int:
 
 class PackedTrack:
     """A whole mono [N] or planar stereo (2, N) track converted once (on the GPU when a context and device tensor are given);
-    slices are cheap.  Stereo frames are interleaved (L, R) like every multichannel WAV."""
+    slices are cheap.  Stereo frames are interleaved (L, R) like every multichannel WAV.  `subtype`: one of `WAV_SUBTYPES`."""
 
     def __init__(self, audio: np.ndarray, sample_rate: int, subtype: str = "PCM_24", *, hip=None, dev=None) -> None:
+        subtype_info(subtype)
         self.sample_rate = int(sample_rate)
         self.subtype = subtype
         self.channels = _channels_of(np.asarray(audio) if dev is None else dev)
@@ -93,29 +148,39 @@ class PackedTrack:
             if self.channels == 2:
                 d = d.t().contiguous().reshape(-1)          # [N, 2]: frame-interleaved, then the mono packing over 2N samples
             self.bytes, self.width = hip.pack_pcm24(d), 3
+        elif hip is not None and self.n > 0:                # the other five: the planar track as it is, interleaved in the kernel
+            d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+            self.bytes, self.width = hip.pack_pcm(d, subtype), subtype_info(subtype)[1]
         else:
             x = np.asarray(audio)
             self.bytes, self.width = pcm_bytes_host(x.T if self.channels == 2 else x, subtype)
 
     @classmethod
-    def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
-        """Wrap PCM_24 bytes that are ready (`ac_mdx_assemble_pcm24`): `3 * channels * n` of them, stereo frames interleaved
-        L, R - the layout the constructor produces."""
+    def from_bytes(cls, data, n: int, channels: int, sample_rate: int, subtype: str) -> "PackedTrack":
+        """Wrap sample bytes of `subtype` that are ready (`ac_mdx_assemble_pcm`): `width * channels * n` of them, stereo frames
+        interleaved L, R - the layout the constructor produces."""
+        width = subtype_info(subtype)[1]
         data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, dtype=np.uint8).reshape(-1)
-        if channels not in (1, 2) or n < 0 or data.size != 3 * channels * n:
-            raise ValueError(f"expected {3 * channels * n} PCM_24 bytes for {n} frames of {channels} channel(s), got {data.size}")
+        if channels not in (1, 2) or n < 0 or data.size != width * channels * n:
+            raise ValueError(f"expected {width * channels * n} {subtype} bytes for {n} frames of {channels} channel(s), got {data.size}")
         track = cls.__new__(cls)
-        track.sample_rate, track.subtype, track.channels, track.n = int(sample_rate), "PCM_24", int(channels), int(n)
-        track.bytes, track.width = data, 3
+        track.sample_rate, track.subtype, track.channels, track.n = int(sample_rate), subtype, int(channels), int(n)
+        track.bytes, track.width = data, width
         return track
+
+    @classmethod
+    def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
+        """`from_bytes` for PCM_24 (`ac_mdx_assemble_pcm24`)."""
+        return cls.from_bytes(data, n, channels, sample_rate, "PCM_24")
 
     def write(self, path: Path, start: int = 0, end: Optional[int] = None) -> Path:
         end = self.n if end is None else end
         start = max(0, min(int(start), self.n)); end = max(start, min(int(end), self.n))
         frame = self.width * self.channels
         with open(path, "wb") as fh:
-            fh.write(wav_header(end - start, self.sample_rate, self.channels, self.width))
+            fh.write(wav_header(end - start, self.sample_rate, self.channels, self.width, self.subtype))
             fh.write(memoryview(self.bytes)[start * frame: end * frame])
+            fh.write(wav_pad(end - start, self.channels, self.width))
         return Path(path)
 
 
@@ -198,4 +263,4 @@ class SegmentExporter:
 
 
 __all__ = ["ensure_supported_format", "build_export_options", "export_audio", "ExportResult", "SegmentExporter", "PackedTrack",
-           "wav_header", "pcm_bytes_host"]
+           "wav_header", "wav_pad", "pcm_bytes_host", "WAV_SUBTYPES", "subtype_info", "configured_subtype"]
