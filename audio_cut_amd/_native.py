@@ -499,18 +499,27 @@ class Context:
             cache[(up, down)] = (self.to_device(self._polyphase_rows(h, up).reshape(-1)), n_pre_remove)
         return cache[(up, down)]
 
+    @staticmethod
+    def _reduced_ratio(up: int, down: int) -> Tuple[int, int]:
+        """(up, down) divided by their greatest common divisor."""
+        import math
+        g = math.gcd(int(up), int(down))
+        return int(up) // g, int(down) // g
+
+    @staticmethod
+    def _resampled_len(n: int, up: int, down: int) -> int:
+        """ceil(n * up / down): librosa's and scipy.signal.resample_poly's output length."""
+        return -(-(n * up) // down)
+
     def resample_poly(self, x: torch.Tensor, up: int, down: int) -> torch.Tensor:
         """x at fs -> fs * up / down on the device: poly-phase FIR in scipy.signal.resample_poly's framing (zero padding, aligned, ceil(n up / down)
         outputs) with the soxr-HQ-specification low-pass of `_resample_filter`."""
-        import math
         self._chk_f32(x)
-        g = math.gcd(int(up), int(down))
-        up, down = int(up) // g, int(down) // g
+        up, down = self._reduced_ratio(up, down)
         if up == down == 1:
             return x.clone()
         n = x.numel()
-        n_out = n * up
-        n_out = n_out // down + bool(n_out % down)
+        n_out = self._resampled_len(n, up, down)
         hd, n_pre_remove = self._resample_filter_dev(up, down)
         out = torch.empty(n_out, dtype=torch.float32, device=self.device)
         _check(self.lib.ac_resample_poly(self._h, _ptr(x), n, up, down, _ptr(hd), hd.numel(), n_pre_remove, _ptr(out), n_out, _stream()))
@@ -521,16 +530,13 @@ class Context:
         `resample_poly` gives converted as `soundfile.write(subtype="PCM_16")` converts it (`pcm_bytes_host(.., "PCM_16")`), in one
         launch (`ac_resample_poly_pcm16`) and one download of 2 bytes per sample; the floats never reach memory.  Equal rates
         after reduction have nothing to resample: the stem is downloaded and converted on the host."""
-        import math
         self._chk_f32(x)
-        g = math.gcd(int(up), int(down))
-        up, down = int(up) // g, int(down) // g
+        up, down = self._reduced_ratio(up, down)
         if up == down == 1:
             from .utils.audio_export import pcm_bytes_host
             return pcm_bytes_host(x.cpu().numpy(), "PCM_16")[0].view("<i2").copy()
         n = x.numel()
-        n_out = n * up
-        n_out = n_out // down + bool(n_out % down)
+        n_out = self._resampled_len(n, up, down)
         hd, n_pre_remove = self._resample_filter_dev(up, down)
         out = torch.empty(-(-n_out // 8) * 8, dtype=torch.int16, device=self.device)      # whole 16-byte groups (the last one zero padded)
         _check(self.lib.ac_resample_poly_pcm16(self._h, _ptr(x), n, up, down, _ptr(hd), hd.numel(), n_pre_remove, _ptr(out), n_out, _stream()))
@@ -540,12 +546,10 @@ class Context:
         """`resample_poly` of every segment x[offsets[s] : offsets[s] + lengths[s]] on its own, one launch.  Returns (out, out_off,
         out_len): segment s's result is out[out_off[s] : out_off[s] + out_len[s]], followed by zeros up to the next multiple of
         `bucket` (0 = no padding)."""
-        import math
         self._chk_f32(x)
-        g = math.gcd(int(up), int(down))
-        up, down = int(up) // g, int(down) // g
+        up, down = self._reduced_ratio(up, down)
         lengths = [int(v) for v in lengths]
-        out_len = [(n * up) // down + bool((n * up) % down) for n in lengths]
+        out_len = [self._resampled_len(n, up, down) for n in lengths]
         padded = [n + ((-n) % bucket if bucket > 0 else 0) for n in out_len]
         out_off = np.concatenate(([0], np.cumsum(padded))).astype(np.int64)
         total = int(out_off[-1])
@@ -584,7 +588,8 @@ class Context:
         return probs
 
     def pack_pcm24(self, x: torch.Tensor) -> np.ndarray:
-        """float32 device track -> host uint8 array of 3 * n little-endian PCM_24 bytes."""
+        """float32 device track -> host uint8 array of 3 * n little-endian PCM_24 bytes: the thin binding of `ac_pack_pcm24`, the
+        mono PCM_24 case of `pack_pcm` under its older name."""
         self._chk_f32(x)
         n = x.numel()
         out = torch.empty(3 * n + 3, dtype=torch.uint8, device=self.device)
@@ -1072,30 +1077,15 @@ class Context:
     ASSEMBLE_PCM24_MAX_PARTIALS = 4096
 
     def mdx_assemble_pcm24(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base):
-        """-> (stem_pcm, rest_pcm, partials): the network's stem and the mix minus it as finished little-endian PCM_24 bytes on the
-        device (uint8 [3 n] for a mono track, [6 n] with frames interleaved L, R for a stereo one: the stems `mdx_assemble_ola`
-        gives, converted as `pack_pcm24` converts them, with no float stem in between) and float64 [3, parts] partial sums of
-        squares of the mono stem, the mono rest and the mono mix, to be added in index order on the host.  One launch
-        (include/audiocut_hip_export.h)."""
-        stereo = self._chk_track(track)
-        n = int(track.shape[-1])
-        if n == 0:
-            raise NativeError("mdx_assemble_pcm24: empty track")
-        ch = 2 if stereo else 1
-        groups = -(-n * ch // 4)
-        parts = min(self.ASSEMBLE_PCM24_MAX_PARTIALS, -(-groups // 256))
-        stem = torch.empty(3 * ch * n, dtype=torch.uint8, device=self.device)
-        rest = torch.empty(3 * ch * n, dtype=torch.uint8, device=self.device)
-        partials = torch.empty((3, parts), dtype=torch.float64, device=self.device)
-        _check(self.lib.ac_mdx_assemble_pcm24(self._h, _ptr(track), n, ch, _ptr(wave), _ptr(chunk_start), _ptr(chunk_len), _ptr(eff_start),
-                                              _ptr(eff_end), _ptr(item_base), chunk_start.numel(), _ptr(stem), _ptr(rest), _ptr(partials),
-                                              parts, _stream()))
-        return stem, rest, partials
+        """`mdx_assemble_pcm(..., "PCM_24")`: uint8 [3 n] per stream for a mono track, [6 n] for a stereo one."""
+        return self.mdx_assemble_pcm(track, wave, chunk_start, chunk_len, eff_start, eff_end, item_base, "PCM_24")
 
     def mdx_assemble_pcm(self, track: torch.Tensor, wave: torch.Tensor, chunk_start, chunk_len, eff_start, eff_end, item_base, subtype: str):
-        """`mdx_assemble_pcm24` with the word of `subtype` (one of the six of `PACK_SUBTYPES`): -> (stem, rest, partials), the two
-        streams as uint8 [n * channels * width] on the device - `pack_pcm` of the stems `mdx_assemble_ola` gives, with no float
-        stem in between - and the same float64 [3, parts] partial sums.  One launch (`ac_mdx_assemble_pcm`)."""
+        """-> (stem_pcm, rest_pcm, partials): the network's stem and the mix minus it as finished sample bytes of `subtype` (one of
+        the six of `PACK_SUBTYPES`) on the device (uint8 [n * channels * width], stereo frames interleaved L, R: `pack_pcm` of the
+        stems `mdx_assemble_ola` gives, with no float stem in between) and float64 [3, parts] partial sums of squares of the mono
+        stem, the mono rest and the mono mix, to be added in index order on the host.  One launch (`ac_mdx_assemble_pcm`,
+        include/audiocut_hip_pack.h)."""
         code, width = pack_subtype(subtype)
         stereo = self._chk_track(track)
         n = int(track.shape[-1])

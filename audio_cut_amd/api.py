@@ -23,7 +23,7 @@ channel mean is `librosa.load(mono=True)`'s; a float file holding a NaN or an in
 `audio.sample_rate` is resampled on the GPU with `ac_resample_poly` (= scipy.signal.resample_poly; the reference's soxr_hq is not
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
-`<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all of the subtype `output.wav.subtype` names (default PCM_24), packed on the GPU (`ac_pack_pcm24`, `ac_pack_pcm`).
+`<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all of the subtype `output.wav.subtype` names (default PCM_24), packed on the GPU (`ac_pack_pcm`).
 Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included, and the lyrics attachment to segments where an alignment
 ran.  `separate_and_segment` returns the manifest like the reference's does.
 

@@ -340,8 +340,8 @@ class EnhancedVocalSeparator:
                       audio_dev: Optional[torch.Tensor] = None) -> SeparationResult:
         """Mode `vocal_separation` (reference `seamless_splitter.py:958-1036`): the separation of `separate_for_detection` and
         nothing of what detection needs.  The iSTFT output goes straight to finished sample bytes of the configured subtype
-        (`output.wav.subtype`; `ac_mdx_assemble_pcm24` for the default PCM_24, `ac_mdx_assemble_pcm` for the other five): the result
-        carries them as `stem_pcm24` (with their `subtype`) and the confidence, no float stems, no feature cache, no VAD segments,
+        (`output.wav.subtype`, default PCM_24; `ac_mdx_assemble_pcm`): the result carries them as `stem_pcm24` (sample bytes of
+        `subtype`, which it names: the key keeps its name for every subtype) and the confidence, no float stems, no feature cache, no VAD segments,
         no markers.  `audio` is a mono [N] or a planar stereo [2, N] float32 track; a stereo track gives two-channel stems."""
         backend = self._primary_backend
         if backend is None:
@@ -364,6 +364,7 @@ class EnhancedVocalSeparator:
             pipeline_used=ctx.enabled, stem_pcm24=pcm)
 
     def _separate_to_pcm24(self, audio, backend: MDX23HipBackend, gpu_context: PipelineContext, audio_dev):
+        """-> (the `stem_pcm24` dictionary: both stems as sample bytes of the configured `subtype`, confidence)."""
         sr = self.sample_rate
         hip = backend.hip
         stereo = np.ndim(audio) == 2

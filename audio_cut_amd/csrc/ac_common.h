@@ -191,7 +191,7 @@ __device__ __forceinline__ void ac_lds_dma16(const void* g, void* lds_wave_base)
 }
 
 
-// ---- rational-rate polyphase FIR (ac_resample_poly, ac_resample_poly_segments) ----------------------------------------------------
+// ---- rational-rate polyphase FIR (the three resamplers of ac_polyphase.hip) -------------------------------------------------------
 // y[m] = sum_q hfull[i - q * up] x[q], i = (m + n_pre_remove) * down, over the n samples of x only (zero extension).  The taps
 // arrive as polyphase ROWS hp[p][t] = hfull[p + t * up] (p < up, t < tpp; rows zero-padded): output m uses row p = i % up against
 // x[i / up - t].  ONE WAVE PER OUTPUT: lane l takes taps t = l, l + 64, ... (a coalesced sweep of the row and of the input run),
@@ -224,7 +224,7 @@ __device__ inline double block_sum_f64_256(double v, double* smem4) {
     return smem4[0] + smem4[1] + smem4[2] + smem4[3];
 }
 
-// ---- float32 -> 24-bit PCM word (ac_pack_pcm24, ac_mdx_assemble_pcm24): libsndfile pcm.c f2let_clip_array, see ac_io.hip ----------
+// ---- float32 -> 24-bit PCM word (ac_pack_pcm, ac_mdx_assemble_pcm): libsndfile pcm.c f2let_clip_array, see ac_pack.hip ------------
 __device__ inline int pcm24(float v) {
     const float s = v * 2147483648.0f;                   // libsndfile: normfact = 8.0 * 0x10000000, product in float32
     if (s >= 2147483647.0f) return 8388607;              // (float)0x7FFFFFFF == 2^31: every s >= 1.0 * 0x7FFFFFFF

@@ -1,6 +1,6 @@
 // The loader's decode (include/audiocut_hip_load.h): the sample bytes of a RIFF/WAVE file, as they stand in the file, to the float32
 // track the pipeline works on - the channel mean of `librosa.load(mono=True)` or planar channels.  The mirror image of the export
-// end's k_pack_pcm24 / k_mdx_assemble_pcm.  A streaming kernel: 64 MB in, 42 MB out for four minutes of 24-bit stereo.
+// end's k_pack_pcm / k_mdx_assemble_pcm.  A streaming kernel: 64 MB in, 42 MB out for four minutes of 24-bit stereo.
 //
 // Work split.  A frame is channels * width bytes, anything from 1 to 64, so neither "a frame per lane" (6-byte lanes: no dword
 // alignment) nor "four frames per lane" (dword aligned, but a lane's span grows to 256 bytes and one load instruction of a wave then

@@ -2,8 +2,14 @@
 // `vocal_separation` mode, -> finished WAV sample bytes of any of the six subtypes the loader reads (8-, 16-, 24- and 32-bit PCM,
 // float32, float64).  Both kernels are streaming kernels: a thread owns a group of four words and a full group leaves as whole
 // 32-bit or wider stores, consecutive threads writing consecutive groups (PCM_32 / FLOAT: 16 bytes per lane, 1 KiB per wave and
-// instruction).  The integer words are the top bytes of pcm32() (ac_common.h), libsndfile's clipping conversion.
+// instruction).  The integer words are the top bytes of pcm32() (ac_common.h), libsndfile's clipping conversion: python-soundfile
+// switches libsndfile's clipping on (SFC_SET_CLIPPING), so soundfile.write(subtype="PCM_24") (`audio_export.py:109-111`) goes
+// through pcm.c f2let_clip_array: s = x * 2^31 in float32; s >= 2^31 - 1 -> 0x7FFFFF, s <= -2^31 -> 0x800000, else the top three
+// bytes of lrintf(s), i.e. lrintf(x * 2^31) >> 8 (a floor, not a rounding, of x * 2^23); the other integer subtypes likewise.
+// The 24-bit entry points of include/audiocut_hip.h and include/audiocut_hip_export.h (ac_pack_pcm24, ac_mdx_assemble_pcm24) are
+// the AC_PACK_PCM_24 instances of these kernels, kept at the end of this file.
 #include "ac_common.h"
+#include "../../include/audiocut_hip_export.h"
 #include "../../include/audiocut_hip_pack.h"
 
 #define MDX_ITEM 261120       // as in ac_mdx.hip
@@ -36,7 +42,7 @@ __device__ inline unsigned pk_word(float v) {
 
 // A thread owns one group of a stream: four words = four mono samples, or two stereo frames (L, R, L, R), 4 * width bytes at
 // out + group * 4 * width, which is aligned to pk_align(ST) when `out` is.  A full group leaves as one dword (PCM_U8), one 8-byte
-// store (PCM_16), three dwords (PCM_24, as k_pack_pcm24 writes them), one 16-byte store (PCM_32, FLOAT) or two (DOUBLE); only the
+// store (PCM_16), three dwords (PCM_24: 12 bytes, 4-byte aligned), one 16-byte store (PCM_32, FLOAT) or two (DOUBLE); only the
 // last group of a track can be partial (count < 4) and leaves byte by byte, so nothing is written past the last word.
 template <int ST>
 __device__ inline void ac_store_pcm_group(unsigned char* __restrict__ out, int64_t group, const float* v, int count) {
@@ -279,4 +285,24 @@ extern "C" int ac_mdx_assemble_pcm(ac_ctx* ctx, const float* track, int64_t n, i
 #undef PK_CASE
     AC_LAUNCH_CHECK();
     return AC_OK;
+}
+
+// ---- the 24-bit entry points: the AC_PACK_PCM_24 instances under their older names ------------------------------------------------
+extern "C" int ac_export_abi_version(void) { return AC_EXPORT_ABI_VERSION; }
+
+// A mono stream of n samples.  The alignment asked of x makes this always k_pack_pcm<1, AC_PACK_PCM_24, true>: a float4 load and
+// three dwords per thread, the last partial group byte by byte.
+extern "C" int ac_pack_pcm24(ac_ctx* ctx, const float* x, int64_t n, unsigned char* out, void* stream) {
+    AC_REQUIRE(ctx && x && out, "null pointer");
+    AC_REQUIRE(n > 0, "n must be positive");
+    AC_REQUIRE((((uintptr_t)x) & 15) == 0 && (((uintptr_t)out) & 3) == 0, "x 16-byte and out 4-byte aligned");
+    return ac_pack_pcm(ctx, x, n, 1, n, AC_PACK_PCM_24, out, stream);     // refuses n >= 2^40 ("track too long"): 4 TB of samples, out of reach
+}
+
+extern "C" int ac_mdx_assemble_pcm24(ac_ctx* ctx, const float* track, int64_t n, int channels, const float* wave,
+                                     const int64_t* chunk_start, const int64_t* chunk_len, const int64_t* eff_start,
+                                     const int64_t* eff_end, const int32_t* item_base, int n_chunks, unsigned char* stem_out,
+                                     unsigned char* rest_out, double* partials, int n_partials, void* stream) {
+    return ac_mdx_assemble_pcm(ctx, track, n, channels, wave, chunk_start, chunk_len, eff_start, eff_end, item_base, n_chunks,
+                               AC_PACK_PCM_24, stem_out, rest_out, partials, n_partials, stream);
 }

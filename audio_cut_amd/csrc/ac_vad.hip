@@ -1,9 +1,8 @@
 // Silero VAD (v5, 16 kHz) on the GPU: the network behind `VocalPauseDetectorV2._detect_speech_timestamps`
 // (`src/vocal_smart_splitter/core/vocal_pause_detector.py:175-296`, reached per chunk from `SileroChunkVAD.process_chunk`,
 // `src/audio_cut/detectors/silero_chunk_vad.py:56-117`).  The reference runs it window by window on the CPU through ONNX
-// Runtime; here all chunks of a track go through four launches:
-//   ac_resample_poly_segments  every chunk's 44.1 kHz -> 16 kHz resampling (`:189`) in one launch, written into a layout
-//                              zero-padded per chunk to the 4096-sample bucket (`:192-196`)
+// Runtime; here all chunks of a track, resampled to 16 kHz into a layout zero-padded per chunk to the 4096-sample bucket
+// (ac_resample_poly_segments, ac_polyphase.hip), go through three launches:
 //   ac_silero_frontend         per window: 64-sample context + 512 samples, reflect pad, STFT-as-convolution (258 x 256 basis,
 //                              stride 128 -> 4 frames), magnitude, four Conv1d + ReLU, and the input half of the LSTM gates
 //                              (W_ih feat + b_ih + b_hh).  Windows are independent here: 8 per workgroup share every weight read.
@@ -22,46 +21,6 @@
 #define SV_PAD 640                       // + 64 reflected
 #define SV_NW 8                          // windows per front-end workgroup
 #define SV_H 128
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Segmented polyphase resampling: ac_resample_poly for S independent segments in one launch.  Output m of segment s is
-// sum_q hfull[(m + n_pre_remove) * down - q * up] x[in_off[s] + q] over the segment's own samples only (zero extension at its
-// edges, as scipy.signal.resample_poly on the segment alone; taps as polyphase rows, ac_common.h); written at out[out_off[s] + m], m < out_len[s].
-__global__ __launch_bounds__(256) void k_resample_poly_seg(const float* __restrict__ x, const int64_t* __restrict__ in_off,
-                                                           const int64_t* __restrict__ in_len, const int64_t* __restrict__ out_off,
-                                                           const int64_t* __restrict__ out_len, int n_seg, int up, int down,
-                                                           const float* __restrict__ hp, int tpp, int64_t n_pre_remove,
-                                                           float* __restrict__ out, int64_t n_work) {
-    // a wave walks AC_RS_PER_WAVE consecutive indices of the concatenation of the segments' (bucket-padded) outputs
-    const int64_t g0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * AC_RS_PER_WAVE;
-    for (int64_t g = g0; g < g0 + AC_RS_PER_WAVE && g < n_work; ++g) {
-        // out_off is increasing and segment s owns [out_off[s], out_off[s] + out_len[s]): binary search over the starts
-        int lo = 0, hi = n_seg - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (out_off[mid] <= g) lo = mid; else hi = mid - 1;
-        }
-        const int64_t m = g - out_off[lo];
-        if (m >= out_len[lo]) continue;                                   // bucket padding: stays zero
-        const float v = ac_polyphase_dot_wave(x + in_off[lo], in_len[lo], hp, up, tpp, (m + n_pre_remove) * (int64_t)down);
-        if ((threadIdx.x & 63) == 0) out[g] = v;
-    }
-}
-
-extern "C" int ac_resample_poly_segments(ac_ctx* ctx, const float* x, const int64_t* in_off, const int64_t* in_len,
-                                         const int64_t* out_off, const int64_t* out_len, int n_seg, int up, int down,
-                                         const float* h, int64_t hlen, int64_t n_pre_remove, float* out, int64_t n_out_total,
-                                         void* stream) {
-    AC_REQUIRE(ctx && x && in_off && in_len && out_off && out_len && h && out, "null pointer");
-    AC_REQUIRE(n_seg > 0 && up > 0 && down > 0 && hlen > 0 && n_pre_remove >= 0 && n_out_total > 0, "sizes must be positive");
-    AC_REQUIRE(hlen % up == 0 && hlen / up < (1LL << 31), "h is [up][hlen / up] polyphase rows");
-    const int64_t blocks = (n_out_total + 4 * AC_RS_PER_WAVE - 1) / (4 * AC_RS_PER_WAVE);
-    AC_REQUIRE(blocks < (1LL << 31), "output too long");
-    hipLaunchKernelGGL(k_resample_poly_seg, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, in_off, in_len,
-                       out_off, out_len, n_seg, up, down, h, (int)(hlen / up), n_pre_remove, out, n_out_total);
-    AC_LAUNCH_CHECK();
-    return AC_OK;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Front end.  LDS images keep the 8 windows of the workgroup innermost ([...][8]) so that one float4 pair feeds the 8 FMAs a

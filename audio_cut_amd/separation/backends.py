@@ -85,8 +85,8 @@ class TrackSeparation:
 
 @dataclass
 class TrackStemsPcm24:
-    """Device-resident result of `MDX23HipBackend.separate_track(export_pcm24=True)`: the stems as finished sample bytes, PCM_24
-    or the `export_subtype` asked for (width = its bytes per word)."""
+    """Device-resident result of `MDX23HipBackend.separate_track(export_pcm24=True)`: the stems as finished sample bytes of
+    the `export_subtype` asked for (width = its bytes per word; PCM_24 by default)."""
 
     vocal: torch.Tensor            # uint8 [width * channels * n]; stereo frames interleaved L, R
     instrumental: torch.Tensor     # uint8 [width * channels * n]
@@ -210,9 +210,9 @@ class MDX23HipBackend(IVocalSeparatorBackend):
         the stream itself and the next one can be queued while this one still runs - `after_launch` is then called as soon as
         everything is queued (the pipeline's gate only has to keep two tracks' launches from interleaving).
         `track_dev` is a mono [N] or a planar stereo [2, N] float32 track; a stereo one also fills `vocal_stereo` / `instrumental_stereo`.
-        `export_pcm24=True` (mode `vocal_separation`): the iSTFT output goes through `ac_mdx_assemble_pcm24` instead of the stem
-        assembly and the per-chunk vocals, and a `TrackStemsPcm24` comes back: no float stem is written.  Not with `unet_stream`.
-        `export_subtype`: the word of those bytes; another than PCM_24 goes through `ac_mdx_assemble_pcm`."""
+        `export_pcm24=True` (mode `vocal_separation`): the iSTFT output goes through `ac_mdx_assemble_pcm` instead of the stem
+        assembly and the per-chunk vocals, and a `TrackStemsPcm24` comes back, the stems as sample bytes of `export_subtype` (any of
+        the six, not only PCM_24: the keyword keeps its name): no float stem is written.  Not with `unet_stream`."""
         if export_pcm24 and unet_stream is not None:
             raise ValueError("export_pcm24 tracks are separated one at a time (no U-Net stream)")
         hip = self.hip
@@ -302,7 +302,8 @@ class MDX23HipBackend(IVocalSeparatorBackend):
 
     def _queue_separation(self, track_dev, n_items, step, timings, ranges, offsets, tables, export_pcm24=False, export_subtype="PCM_24"):
         """Queues STFT -> U-Net -> iSTFT of every sub-batch and the stem assembly on the CURRENT stream; no host synchronisation.
-        `export_pcm24`: the assembly is `ac_mdx_assemble_pcm24` and the result (vocal bytes, instrumental bytes, partials, events)."""
+        `export_pcm24`: the assembly is `ac_mdx_assemble_pcm`, which writes sample bytes of `export_subtype`, and the result
+        (vocal bytes, instrumental bytes, partials, events)."""
         hip = self.hip
         net = self.net
         d_cs, d_cl, d_wi, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, d_offsets = tables
@@ -324,11 +325,7 @@ class MDX23HipBackend(IVocalSeparatorBackend):
                 ev[3].record()
                 events.append(ev)
         if export_pcm24:        # an instrumental-type network: the two streams, and the first two rows of the partials, change places
-            if export_subtype == "PCM_24":
-                stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm24(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base)
-            else:
-                stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base,
-                                                                    export_subtype)
+            stem_pcm, rest_pcm, partials = hip.mdx_assemble_pcm(track_dev, wave, d_chunk_start, d_chunk_len, d_es, d_ee, d_base, export_subtype)
             if self.get_output_type() == "vocal":
                 return stem_pcm, rest_pcm, partials, events
             return rest_pcm, stem_pcm, partials[[1, 0, 2]], events

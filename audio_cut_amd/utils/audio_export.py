@@ -3,15 +3,14 @@
 formats this build writes: WAV of the subtypes PCM_24 (the reference default, `audio_export.py:109-111`), PCM_U8, PCM_16, PCM_32,
 FLOAT and DOUBLE (`output.wav.subtype`, what `soundfile.write(.., subtype=..)` gets there).  SURVEY.md §8(f) row 4.
 
-The float -> integer conversion runs on the GPU (`ac_pack_pcm24`, `ac_pack_pcm`) on the whole resident track once and is libsndfile's
+The float -> integer conversion runs on the GPU (`ac_pack_pcm`, one kernel for all six subtypes) on the whole resident track once and is libsndfile's
 clipping conversion - python-soundfile sets SFC_SET_CLIPPING on every file, so `soundfile.write` goes through pcm.c
 `f2let_clip_array`: `lrintf(x * 2^31) >> 8`, saturating at 0x7FFFFF / 0x800000 (`>> 16` for PCM_16, `>> 24` plus 128 for PCM_U8, the
 whole word for PCM_32); FLOAT is the float32 bits as they are and DOUBLE their exact widening, nothing clipped.  Segment files are
 byte slices of that buffer behind a RIFF header (44 bytes for the integer subtypes, 56 with the `fact` chunk of the float ones).
 MP3 needs pydub + FFmpeg in the reference (`:114-135`) and is refused here.
 Stereo tracks are planar (2, N) arrays (the reference writes `(channels, samples)` arrays as multichannel files, `:93-106`): they
-are interleaved frame by frame (in the packing kernel; PCM_24 as [N, 2] on the device before `ac_pack_pcm24`) and the header
-carries two channels.
+are interleaved frame by frame in the packing kernel, which reads the planar rows as they are, and the header carries two channels.
 """
 from __future__ import annotations
 
@@ -143,12 +142,7 @@ class PackedTrack:
         self.subtype = subtype
         self.channels = _channels_of(np.asarray(audio) if dev is None else dev)
         self.n = int(np.shape(audio)[-1])
-        if subtype == "PCM_24" and hip is not None and self.n > 0:
-            d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
-            if self.channels == 2:
-                d = d.t().contiguous().reshape(-1)          # [N, 2]: frame-interleaved, then the mono packing over 2N samples
-            self.bytes, self.width = hip.pack_pcm24(d), 3
-        elif hip is not None and self.n > 0:                # the other five: the planar track as it is, interleaved in the kernel
+        if hip is not None and self.n > 0:                  # the planar track as it is, interleaved in the kernel
             d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
             self.bytes, self.width = hip.pack_pcm(d, subtype), subtype_info(subtype)[1]
         else:
@@ -170,7 +164,7 @@ class PackedTrack:
 
     @classmethod
     def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
-        """`from_bytes` for PCM_24 (`ac_mdx_assemble_pcm24`)."""
+        """`from_bytes` for PCM_24."""
         return cls.from_bytes(data, n, channels, sample_rate, "PCM_24")
 
     def write(self, path: Path, start: int = 0, end: Optional[int] = None) -> Path:

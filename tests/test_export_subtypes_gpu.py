@@ -101,6 +101,35 @@ def test_pack_pcm_rows_and_alignment(hip_ctx, subtype):
         assert _pack_checked(hip_ctx, base[offset:], subtype).tobytes() == want.tobytes(), (subtype, n, offset)
 
 
+@pytest.mark.parametrize("channels", [1, 2])
+@pytest.mark.parametrize("subtype", ["PCM_24", "PCM_16"])
+def test_packed_track_on_a_device_track(hip_ctx, subtype, channels):
+    """`PackedTrack` with a context and a device track (one `ac_pack_pcm` launch on the planar track as it is, for every subtype)
+    holds the bytes of `PackedTrack` without a context (the host conversion).  A stereo track once contiguous and once as rows
+    that are views into wider rows, at an even stride (the 8-byte loads) and an odd one (sample by sample); the frame counts give
+    a lone partial group, full groups, and a partial last group in a workgroup of its own (1025 frames).  Stereo PCM_24 used to be
+    transposed on the device and packed as 2N mono samples: that route, rebuilt here, gives the same bytes."""
+    for n in (1, 2, 3, 4, 5, 1025):
+        x = _input(n, channels, n % 4)                              # [channels, n]
+        x_host = x if channels == 2 else x[0]
+        want = AE.PackedTrack(x_host, SR, subtype)
+        tracks = [hip_ctx.to_device(x_host)]
+        if channels == 2:
+            for stride in (n + n % 2 + 2, n + n % 2 + 3):
+                base = torch.full((2, stride), 7.0, dtype=torch.float32, device=hip_ctx.device)
+                base[:, :n] = tracks[0]
+                tracks.append(base[:, :n])
+                assert tracks[-1].stride(0) == stride and not tracks[-1].is_contiguous()
+        for xd in tracks:
+            got = AE.PackedTrack(x_host, SR, subtype, hip=hip_ctx, dev=xd)
+            assert (got.n, got.channels, got.width, got.subtype) == (want.n, want.channels, want.width, want.subtype) == \
+                (n, channels, WIDTH[subtype], subtype)
+            assert np.asarray(got.bytes).tobytes() == np.asarray(want.bytes).tobytes(), (subtype, channels, n, xd.stride(0))
+            if channels == 2 and subtype == "PCM_24":
+                old = hip_ctx.pack_pcm24(xd.t().contiguous().reshape(-1))
+                assert np.asarray(got.bytes).tobytes() == old.tobytes(), (n, xd.stride(0))
+
+
 def test_pack_pcm_wrapper_refusals(hip_ctx):
     from audio_cut_amd import _native
     dev = hip_ctx.device

@@ -205,7 +205,7 @@ def test_local_valley_edges(hip_ctx, track):
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("up,down", [(160, 441), (3, 2), (7, 7)])
 def test_resample_poly_segments_edges(hip_ctx, track, up, down):
-    """Every segment is `resample_poly` of the segment alone, bit for bit (ac_vad.hip: scipy.signal.resample_poly on the segment
+    """Every segment is `resample_poly` of the segment alone, bit for bit (ac_polyphase.hip: scipy.signal.resample_poly on the segment
     alone), and within 2e-6 of the float64 oracle (the float32 polyphase dot against float64 scipy: the precedent of
     `test_resample_poly_kernel_vs_oracle`); bucket padding is exactly 0.0.  Lengths 0, 1, 2, 159, 160, 441, 442 and one whose output
     is an exact multiple of the 4096 bucket; buckets 0 and 4096; up == down (a copy).  The 2e-6 covers only the filter DESIGN

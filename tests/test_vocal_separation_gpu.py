@@ -1,4 +1,4 @@
-"""Mode `vocal_separation` on the GPU: k_mdx_assemble_pcm24<1|2> (audio_cut_amd/csrc/ac_export.hip) byte for byte against the kernels
+"""Mode `vocal_separation` on the GPU: k_mdx_assemble_pcm<1|2, PCM_24> (audio_cut_amd/csrc/ac_pack.hip) byte for byte against the kernels
 it stands in for and against the oracle, with no U-Net involved, and the mode end to end against a `v2.2_mdd` run of the same
 input in the same process.
 

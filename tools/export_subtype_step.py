@@ -9,7 +9,7 @@ on the host as `_split_and_export` has them after `split_track`.  No U-Net runs 
     conversion kernel and one download each), the mix segments and the vocal segments (8 s pieces) and the two full stems written
     under a temporary directory.  Host clock between two device synchronisations, the subtypes alternated, `--steps` runs each
     after `--warmup`.  Variants: the six subtypes; `PCM_24 again`, the same call a second time per round (the spread of one code
-    path beside itself: PCM_24 goes through `ac_pack_pcm24` as it always did); `PCM_16 host`, the conversion PCM_16 had before it
+    path beside itself: every subtype goes through `ac_pack_pcm`); `PCM_16 host`, the conversion PCM_16 had before it
     moved to the device (`pcm_bytes_host` over the host copy of the float track, what `PackedTrack` without a context does).
 (2) `ac_mdx_assemble_pcm` (fused: iSTFT waves -> both stems' bytes + energy partials) beside `ac_mdx_assemble_ola` followed by
     `ac_pack_pcm` of both stems (the energy sums left out of the unfused side), between two device events, on a hand-made plan of
@@ -119,7 +119,7 @@ def main() -> None:
     xd = dev["mix"]
 
     def fused(subtype):
-        return hip.mdx_assemble_pcm24(xd, wave, *tables) if subtype == "PCM_24" else hip.mdx_assemble_pcm(xd, wave, *tables, subtype)
+        return hip.mdx_assemble_pcm(xd, wave, *tables, subtype)
 
     def unfused(subtype):
         v, i, _, _ = hip.mdx_assemble_ola(xd, wave, *tables)

@@ -10,7 +10,7 @@ a host clock between two device synchronisations:
   * `track_ms`: one splitter kept, `split_track` plus writing the two stem files - the per-track work the modes differ in.
 Prints one JSON line: median, min and max per mode, the differences of the medians, and whether the files of the two modes hold
 the same bytes.  Under `rocprofv3 --kernel-trace --stats -- python tools/vocal_separation_step.py --api-steps 0` the kernel
-statistics give k_mdx_assemble_pcm (the PCM_24 instance) beside k_mdx_assemble_ola + k_pack_pcm24 + k_sum_squares."""
+statistics give k_mdx_assemble_pcm (the PCM_24 instance) beside k_mdx_assemble_ola + k_pack_pcm (its PCM_24 instance) + k_sum_squares."""
 from __future__ import annotations
 
 import argparse
