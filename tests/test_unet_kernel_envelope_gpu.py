@@ -23,11 +23,14 @@ def _i16(ctx, packed):
     return torch.from_numpy(packed.view(np.int16)).to(ctx.device)
 
 
-def run_case(ctx, case, in_amax=None, out_amax=None):
-    """the kernel of `case` on its tensors (weights packed by conv_pack as the product does)."""
-    d = {k: v.to(ctx.device) for k, v in case.t.items()}
+def run_case(ctx, case, in_amax=None, out_amax=None, upload=None, out=None):
+    """the kernel of `case` on its tensors (weights packed by conv_pack as the product does).  `upload`: how a host tensor reaches the
+    device (default `.to(ctx.device)`); `out`: passed on as `out=` by the 3x3 convs, the wrappers that take one."""
+    put = (lambda t: t.to(ctx.device)) if upload is None else (lambda t: upload(t.contiguous().numpy()))
+    d = {k: put(v) for k, v in case.t.items()}
     s, kind = case.shapes, case.kind
-    ia = None if in_amax is None else in_amax.to(ctx.device)
+    ia = None if in_amax is None else put(in_amax)
+    _i16 = lambda c, packed: put(torch.from_numpy(packed.view(np.int16)))
     if kind in ("conv", "conv_s8", "conv_w96", "first"):
         w = case.t["w"].numpy()
         packed, un = CP.pack_conv3x3(w) if kind == "conv" else CP.pack_conv3x3_w96(w, 96 if kind == "conv_w96" else 48)
@@ -37,13 +40,13 @@ def run_case(ctx, case, in_amax=None, out_amax=None):
             return ctx.conv3x3_f16x3_first(d["spec"], d["w1"], d["b1"], _i16(ctx, packed), d["bias"], s["Co"], un, relu=relu, spec_amax=ia,
                                            amax_gain=gain, amax_offs=offs, out_amax=out_amax)
         fn = {"conv": ctx.conv3x3_f16x3, "conv_s8": ctx.conv3x3_f16x3_s8, "conv_w96": ctx.conv3x3_f16x3_w96}[kind]
-        return fn(d["x"], _i16(ctx, packed), d["bias"], s["Co"], un, relu=relu, in_amax=ia, out_amax=out_amax)
+        return fn(d["x"], _i16(ctx, packed), d["bias"], s["Co"], un, relu=relu, out=out, in_amax=ia, out_amax=out_amax)
     if kind == "tdf":
         packed, un = CP.pack_linear(case.t["w"].numpy())
         return ctx.tdf_linear_f16x3(d["x"], _i16(ctx, packed), s["N"], d["scale"], d["shift"], un, resid=d.get("resid"), in_amax=ia, out_amax=out_amax)
     if kind == "tdf_small":
         p1, p2 = CP.pack_tdf_small(case.t["w1"].numpy(), case.t["w2"].numpy())
-        return ctx.tdf_small_fused(d["x"], torch.from_numpy(p1).to(ctx.device), torch.from_numpy(p2).to(ctx.device), s["Hd"], d["s1"], d["b1"],
+        return ctx.tdf_small_fused(d["x"], put(torch.from_numpy(p1)), put(torch.from_numpy(p2)), s["Hd"], d["s1"], d["b1"],
                                    d["s2"], d["b2"], out_amax=out_amax)
     if kind in ("down", "up"):
         packed, un = CP.pack_linear(case.t["wm"].numpy(), bn=96)
