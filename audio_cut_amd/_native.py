@@ -61,6 +61,8 @@ def load() -> C.CDLL:
         raise NativeError("libaudiocut_hip.so loader ABI version mismatch")
     if lib.ac_pack_abi_version() != 1:
         raise NativeError("libaudiocut_hip.so pack ABI version mismatch")
+    if lib.ac_rate_abi_version() != 1:
+        raise NativeError("libaudiocut_hip.so rate ABI version mismatch")
     _lib = lib
     return lib
 
@@ -193,6 +195,13 @@ PACK_SIGNATURES = {
     "ac_pack_pcm": (C.c_int, [_P, _P, _I64, _I, _I64, _I, _P, _P]),
     "ac_mdx_assemble_pcm": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
 }
+# include/audiocut_hip_rate.h: export at another sample rate (the resident stem -> finished sample bytes of any subtype at
+# fs * up / down, mono or stereo, one launch), exported by the same library and versioned on its own.  The wrapper is
+# utils/rate_export.py `resample_pack_device`.
+RATE_SIGNATURES = {
+    "ac_rate_abi_version": (C.c_int, []),
+    "ac_resample_poly_pack": (C.c_int, [_P, _P, _I64, _I, _I64, _I, _I, _P, _I64, _I64, _I, _P, _I64, _P]),
+}
 # subtype name -> (AC_PACK_* code, bytes per word), and the lookup that refuses every other name: one table for the host conversion,
 # the WAV header and these bindings
 from .utils.audio_export import WAV_SUBTYPES as PACK_SUBTYPES, subtype_info as pack_subtype  # noqa: E402
@@ -215,7 +224,7 @@ def coverage_from(peak: float, count: int, n: int) -> float:
 def _declare(lib: C.CDLL) -> None:
     for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
                               *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items(),
-                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items(), *PACK_SIGNATURES.items()):
+                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items(), *PACK_SIGNATURES.items(), *RATE_SIGNATURES.items()):
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

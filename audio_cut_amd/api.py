@@ -24,6 +24,8 @@ channel mean is `librosa.load(mono=True)`'s; a float file holding a NaN or an in
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
 `<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all of the subtype `output.wav.subtype` names (default PCM_24), packed on the GPU (`ac_pack_pcm`).
+`output.sample_rate` (`"source"` or an integer; absent by default; INTEGRATION.md, "Export rate") lets the files leave at another rate than
+`audio.sample_rate`: the stems through `ac_resample_poly_pack` (`utils/rate_export.py`), the mix at the file's own rate as it was loaded.
 Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included, and the lyrics attachment to segments where an alignment
 ran.  `separate_and_segment` returns the manifest like the reference's does.
 
@@ -46,6 +48,7 @@ from .config.auto_profile import resolve_smart_cut_intent
 from .core.seamless_splitter import SeamlessSplitter
 from .lyrics.models import LyricsTimeline
 from .lyrics.segment_attach import attach_lyrics_to_segments
+from .utils.rate_export import map_cut, rate_ratio, resampled_len, resolve_output_rate
 from .utils.wav_reader import LAYOUT_MONO, LAYOUT_PLANAR, channel_mean, read_wav, read_wav_bytes, read_wav_info
 
 
@@ -291,14 +294,27 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter, configured_subtype
     t_start = time.time()
     subtype = configured_subtype()          # `output.format` / `output.wav.subtype`: refused here, before any work, if not written
+    # `output.sample_rate` (utils/rate_export.py): the rate the files leave at, resolved - and refused - from the file's header
+    # alone, before the track is loaded.  Absent: `out_sr` is `sr` and nothing below differs from a build without the setting.
+    rate_set = _config.get_config("output.sample_rate", None) is not None
+    out_sr, source_sr = sr, sr
+    if rate_set:
+        source_sr = sr if in_path.suffix.lower() == ".npy" else int(read_wav_info(in_path).sample_rate)
+        out_sr = resolve_output_rate(source_sr, sr)
+        if mode == "vocal_separation" and out_sr != sr:
+            raise ValueError(f"output.sample_rate {out_sr} with mode 'vocal_separation': that mode writes its bytes straight from the "
+                             f"iSTFT and has no float stem to resample, so it exports at audio.sample_rate ({sr}) only; mode "
+                             f"'v2.2_mdd' with export_types=[\"full_vocal\", \"full_instrumental\"] writes the same two files at {out_sr} Hz")
     splitter = SeamlessSplitter(sample_rate=sr, device=device)
     hip = splitter._context()
     audio_dev = None
+    source_track = None         # the track in front of the load resampler (device or host), kept when the files leave at its rate
     if in_path.suffix.lower() == ".wav" and bool(_config.get_config("audio.gpu_decode", True)):
         # the file's bytes are decoded on the device (`load_audio_device`); the host copy of the track is one download
         audio_dev, file_sr = load_audio_device(str(in_path), hip, channels)
         if file_sr != sr:                     # as below: per channel for two channels, the mono mean for one
             import torch
+            source_track = audio_dev if out_sr == file_sr else None
             audio_dev = torch.stack([hip.resample_poly(audio_dev[c].contiguous(), sr, file_sr) for c in range(2)]) if channels == 2 \
                 else hip.resample_poly(audio_dev, sr, file_sr)
         audio = audio_dev.cpu().numpy()
@@ -306,11 +322,13 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         audio, file_sr = load_audio_stereo(str(in_path))
         if file_sr != sr:                     # each channel on its own; detection then reads the mean of the resampled channels
             import torch
+            source_track = audio if out_sr == file_sr else None
             audio_dev = torch.stack([hip.resample_poly(hip.to_device(audio[c]), sr, file_sr) for c in range(2)])
             audio = audio_dev.cpu().numpy()
     else:
         audio, file_sr = load_audio_mono(str(in_path))
         if file_sr != sr:
+            source_track = audio if out_sr == file_sr else None
             audio_dev = hip.resample_poly(hip.to_device(audio), sr, file_sr)     # e.g. 48 kHz -> 44.1 kHz = up 147 / down 160
             audio = audio_dev.cpu().numpy()
     # `vpbd_asr`: the detector writes the 16 kHz ASR copy of the vocal stem next to the exports, named after the input
@@ -345,15 +363,34 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     # the tracks written: mono, or with two channels the stereo mix and stems ([2, N], host and device)
     st = "_stereo" if channels == 2 else ""
     mix_dev = state.get("mix_stereo", audio_dev) if channels == 2 else state.get("mix", audio_dev)
+    n = int(np.shape(audio)[-1])
+    if out_sr == sr:
+        n_out, out_spans = n, spans
+
+        def packed(track, dev):
+            return PackedTrack(track, sr, subtype, hip=hip, dev=dev)
+    else:
+        # every exported track has n_out frames: the file's own count at the file's rate (the stems are cropped to it, never padded),
+        # else what the resampler gives; every span end goes to its nearest frame there and the end of the track to n_out, so the
+        # segments of a kind are consecutive byte ranges of the one converted track
+        n_out = int(np.shape(source_track)[-1]) if source_track is not None else resampled_len(n, *rate_ratio(out_sr, sr))
+        out_spans = [(map_cut(lo, sr, out_sr, n_out, n), map_cut(hi, sr, out_sr, n_out, n)) for lo, hi in spans]
+
+        def packed(track, dev):
+            return PackedTrack.resampled(track, sr, out_sr, n_out, subtype, hip=hip, dev=dev)
     if "mix_segments" in plan:
-        mix_pk = PackedTrack(audio, sr, subtype, hip=hip, dev=mix_dev)
-        exp.mix_segment_files = exporter.export_spans(mix_pk, spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap,
+        if source_track is not None:        # the loaded track as it was in front of the load resampler: nothing is resampled twice
+            is_dev = not isinstance(source_track, np.ndarray)
+            mix_pk = PackedTrack(source_track, out_sr, subtype, hip=hip, dev=source_track if is_dev else None)
+        else:
+            mix_pk = packed(audio, mix_dev)
+        exp.mix_segment_files = exporter.export_spans(mix_pk, out_spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap,
                                                       **naming)
         exp.saved_files += exp.mix_segment_files
     vocal = res.get("vocal_track" + st)
-    voc_pk = PackedTrack(vocal, sr, subtype, hip=hip, dev=state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
+    voc_pk = packed(vocal, state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
     if "vocal_segments" in plan and voc_pk is not None:
-        exp.vocal_segment_files = exporter.export_spans(voc_pk, spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
+        exp.vocal_segment_files = exporter.export_spans(voc_pk, out_spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
                                                         file_suffix="_vocal", duration_map=dmap, **naming)
         exp.saved_files += exp.vocal_segment_files
     if "full_vocal" in plan and voc_pk is not None:
@@ -361,7 +398,7 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         exp.saved_files.append(exp.full_vocal_file)
     inst = res.get("instrumental_track" + st)
     if "full_instrumental" in plan and inst is not None:
-        inst_pk = PackedTrack(inst, sr, subtype, hip=hip, dev=state.get("instrumental" + st))
+        inst_pk = packed(inst, state.get("instrumental" + st))
         exp.full_instrumental_file = exporter.export_full_track(inst_pk, out_dir / f"{in_path.stem}_{mode}_instrumental_{np.shape(inst)[-1] / float(sr):.1f}")
         exp.saved_files.append(exp.full_instrumental_file)
     out: Dict[str, Any] = {
@@ -383,6 +420,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         "full_instrumental_file": exp.full_instrumental_file,
         "timings": res.get("timings", {}), "processing_time": time.time() - t_start,
     }
+    if rate_set:        # `output.sample_rate`: what the files are at; `sample_rate` and `cut_points_samples` stay the pipeline's
+        out.update({"export_sample_rate": out_sr, "source_sample_rate": source_sr,
+                    "export_cut_points_samples": [c if out_sr == sr else map_cut(c, sr, out_sr, n_out, n) for c in cuts]})
     if res.get("note"):
         out["note"] = res["note"]
     if smart:       # `:1341-1347`, and the bar analysis behind the cuts
@@ -547,6 +587,9 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
         "timings_ms": {"total": _to_ms(result.get("processing_time"))},
         "stats": {"num_segments": int(result.get("num_segments", 0))},
     }
+    if result.get("export_sample_rate") is not None:                                      # `output.sample_rate` was set
+        manifest["export"] = {"sr": result["export_sample_rate"], "source_sr": result.get("source_sample_rate"),
+                              "cuts_samples": result.get("export_cut_points_samples", [])}
     if result.get("note"):
         manifest["note"] = result["note"]
     for block in ("lyrics_alignment", "boundary_detection", "auto_profile", "intent"):

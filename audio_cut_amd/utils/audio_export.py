@@ -163,6 +163,23 @@ class PackedTrack:
         return track
 
     @classmethod
+    def resampled(cls, audio, sample_rate: int, out_rate: int, n_out: int, subtype: str = "PCM_24", *, hip=None, dev=None) -> "PackedTrack":
+        """This track (at `sample_rate`), resampled to `out_rate` and cropped to `n_out` frames (`output.sample_rate`): with a
+        context, one launch of `ac_resample_poly_pack` on the device track (`utils/rate_export.py`) and one download of the
+        finished bytes - no float track at `out_rate` exists anywhere; without one, `resample_pack_host`.  `sample_rate` of the
+        result is `out_rate`; equal rates give the constructor's bytes, cropped."""
+        from .rate_export import rate_ratio, resample_pack_device, resample_pack_host
+        subtype_info(subtype)
+        up, down = rate_ratio(out_rate, sample_rate)
+        channels = _channels_of(np.asarray(audio) if dev is None else dev)
+        if hip is not None:
+            d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
+            data = resample_pack_device(hip, d, up, down, subtype, int(n_out)).cpu().numpy()
+        else:
+            data = resample_pack_host(np.asarray(audio), up, down, subtype, int(n_out))
+        return cls.from_bytes(data, int(n_out), channels, int(out_rate), subtype)
+
+    @classmethod
     def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
         """`from_bytes` for PCM_24."""
         return cls.from_bytes(data, n, channels, sample_rate, "PCM_24")
