@@ -10,7 +10,7 @@ import ctypes as C
 import threading
 import os
 from pathlib import Path
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -39,30 +39,10 @@ def load() -> C.CDLL:
                           f"(there is no CPU fallback for the HIP path)")
     lib = C.CDLL(str(path))
     _declare(lib)
-    if lib.ac_abi_version() != 6:
-        raise NativeError("libaudiocut_hip.so ABI version mismatch")
-    if lib.ac_stereo_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so stereo ABI version mismatch")
-    if lib.ac_onset_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so onset ABI version mismatch")
-    if lib.ac_beat_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so beat ABI version mismatch")
-    if lib.ac_hybrid_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so hybrid ABI version mismatch")
-    if lib.ac_export_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so export ABI version mismatch")
-    if lib.ac_asr_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so asr ABI version mismatch")
-    if lib.ac_profile_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so profile ABI version mismatch")
-    if lib.ac_final_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so final-layer ABI version mismatch")
-    if lib.ac_load_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so loader ABI version mismatch")
-    if lib.ac_pack_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so pack ABI version mismatch")
-    if lib.ac_rate_abi_version() != 1:
-        raise NativeError("libaudiocut_hip.so rate ABI version mismatch")
+    for s in ABI_SURFACES:
+        found = getattr(lib, s.version_fn)()
+        if found != s.version:
+            raise NativeError(f"{_LIB_NAME}: include/{s.header} is at ABI version {found}, this binding expects {s.version}")
     _lib = lib
     return lib
 
@@ -71,137 +51,140 @@ _P = C.c_void_p
 _I64 = C.c_int64
 _I = C.c_int
 
-SIGNATURES = {
-    "ac_abi_version": (C.c_int, []),
-    "ac_last_error": (C.c_char_p, []),
-    "ac_ctx_create": (C.c_int, [_I, C.POINTER(_P)]),
-    "ac_ctx_destroy": (C.c_int, [_P]),
-    "ac_frame_rms": (C.c_int, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P]),
-    "ac_frame_rms_multi": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
-    "ac_stft2048_features": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _P]),
-    "ac_onset_strength": (C.c_int, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P]),
-    "ac_tempogram_parts": (C.c_int, [_I64]),
-    "ac_tempogram_reduce": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
-    "ac_yin_f0": (C.c_int, [_P, _P, _I64, _I, _I, _I, _I, C.c_double, _P, _P, _I64, _P]),
-    "ac_moving_meansq_db_f64": (C.c_int, [_P, _P, _I64, _I, _P, _P]),
-    "ac_next_leq_scratch": (C.c_int64, [_I64]),
-    "ac_next_leq_scan": (C.c_int, [_P, _P, _I64, C.c_double, _P, _P, _P]),
-    "ac_window_argmin_f64": (C.c_int, [_P, _P, _I64, _P, _P, _I, _P, _P, _P]),
-    "ac_zero_cross_nearest": (C.c_int, [_P, _P, _I64, _P, _I, _I, _P, _P]),
-    "ac_quiet_guard_slow": (C.c_int, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P]),
-    "ac_pause_cut_points": (C.c_int, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P]),
-    "ac_mdx_stft": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I, _P, _P, _P]),
-    "ac_mdx_istft": (C.c_int, [_P, _P, _I, _P, _P, _P]),
-    "ac_mdx_assemble_ola": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
-    "ac_mdx_chunk_vocal": (C.c_int, [_P, _P, _P, _P, _P, _I, _P, _P]),
-    "ac_sum_squares": (C.c_int, [_P, _P, _I64, _P, _I, _P]),
-    "ac_window_sum_squares": (C.c_int, [_P, _P, _I64, _P, _P, _I, _P, _P]),
-    "ac_conv3x3_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P]),
-    "ac_conv3x3_f16x3_w96": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P]),
-    "ac_conv3x3_f16x3_s8": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _I, _P, _P, _P]),
-    "ac_conv3x3_f16x3_first": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_float, _I, _P, C.c_float, C.c_float,
-                                         _P, _P]),
-    "ac_tdf_linear_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, C.c_float, _P, _P, _P]),
-    "ac_tdf_small_fused": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _P, _P]),
-    "ac_conv1x1_small": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I64, _I, _P]),
-    "ac_down2x_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P]),
-    "ac_up2x_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, C.c_float, _P, _P, _P]),
-    "ac_pyin_observe": (C.c_int, [_P, _P, _I64, _I, _I, C.c_double, C.c_double, _I, _I, _P, _P, _P, _P, _P, C.c_double, C.c_double,
-                                  _P, _P, _P, _P]),
-    "ac_pyin_viterbi": (C.c_int, [_P, _P, _P, _I64, _I, _I, _P, _P, C.c_double, _P, _P, _P, _P]),
-    "ac_lpc_formants": (C.c_int, [_P, _P, _I64, _I, _I, _I, C.c_float, _P, _P, _I64, _P]),
-    "ac_zero_crossing_rate": (C.c_int, [_P, _P, _I64, _I, _I, _P, _I64, _P]),
-    "ac_stft2048_spectral": (C.c_int, [_P, _P, _I64, _I, C.c_double, _P, _P, _I64, _P]),
-    "ac_segment_frame_rms": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I, _I, _I, _I, _P, _I64, _P]),
-    "ac_segment_sumsq_peak": (C.c_int, [_P, _P, _I64, _P, _P, _I, _P, _P, _P]),
-    "ac_local_valley_tiles": (C.c_int, [_I, _I]),
-    "ac_local_valley": (C.c_int, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "ac_resample_poly": (C.c_int, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
-    "ac_pack_pcm24": (C.c_int, [_P, _P, _I64, _P, _P]),
-    "ac_resample_poly_segments": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
-    "ac_silero_frontend": (C.c_int, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "ac_silero_lstm": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P]),
-    "ac_silero_out": (C.c_int, [_P, _P, _P, C.c_float, _I, _P, _P]),
-    "ac_host_beat_dp": (C.c_int, [_P, _I64, C.c_double, C.c_double, _P, _P]),
-}
-
-# include/audiocut_hip_stereo.h: the true-stereo extension, exported by the same library and versioned on its own
-STEREO_SIGNATURES = {
-    "ac_stereo_abi_version": (C.c_int, []),
-    "ac_mdx_stft_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _I, _P, _P, _P]),
-    "ac_mdx_assemble_ola_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
-    "ac_mdx_chunk_vocal_stereo": (C.c_int, [_P, _P, _I64, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
-}
+_F = C.c_float
+_D = C.c_double
 
 
-# include/audiocut_hip_onset.h: the `librosa_onset` mode's reductions, exported by the same library and versioned on their own
-ONSET_SIGNATURES = {
-    "ac_onset_abi_version": (C.c_int, []),
-    "ac_bar_energy_silence": (C.c_int, [_P, _P, _I64, _P, _P, _I, C.c_double, _P, _P, _P]),
-    "ac_segment_pair_energy": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I, _P, _P]),
-}
+class AbiSurface(NamedTuple):
+    """One header under include/: all headers are exported by the same library, each is versioned on its own."""
+    header: str             # file name under include/
+    version_fn: str         # the export that returns the header's AC_<X>_ABI_VERSION
+    version: int            # the version these signatures were written for: load() refuses a library at another
+    signatures: dict        # export -> (restype, [argtypes]), version_fn included
 
-# include/audiocut_hip_beat.h: the beat / bar analysis layer's spectral series and per-bar means, exported by the same library and
-# versioned on their own
-BEAT_SIGNATURES = {
-    "ac_beat_abi_version": (C.c_int, []),
-    "ac_stft2048_centroid_bandwidth": (C.c_int, [_P, _P, _I64, _I, C.c_double, _P, _P, _I64, _P]),
-    "ac_bar_means3": (C.c_int, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I, _P, _P]),
-}
 
-# include/audiocut_hip_hybrid.h: the `hybrid_mdd` mode's quiet gate, exported by the same library and versioned on its own
-HYBRID_SIGNATURES = {
-    "ac_hybrid_abi_version": (C.c_int, []),
-    "ac_quiet_gate_meansq": (C.c_int, [_P, _P, _I64, _I64, _P, _I, _P, _I64, _P, _P, _P]),
-}
+# The whole C ABI, one row per header.  tests/test_abi_surfaces.py holds every row against its header, type by type.
+ABI_SURFACES = (
+    # include/audiocut_hip.h: the context, the error plumbing and every entry point older than the extension headers
+    AbiSurface("audiocut_hip.h", "ac_abi_version", 6, {
+        "ac_abi_version": (_I, []),
+        "ac_last_error": (C.c_char_p, []),
+        "ac_ctx_create": (_I, [_I, C.POINTER(_P)]),
+        "ac_ctx_destroy": (_I, [_P]),
+        "ac_frame_rms": (_I, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P]),
+        "ac_frame_rms_multi": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
+        "ac_stft2048_features": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _P]),
+        "ac_onset_strength": (_I, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P]),
+        "ac_tempogram_parts": (_I, [_I64]),
+        "ac_tempogram_reduce": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P]),
+        "ac_yin_f0": (_I, [_P, _P, _I64, _I, _I, _I, _I, _D, _P, _P, _I64, _P]),
+        "ac_moving_meansq_db_f64": (_I, [_P, _P, _I64, _I, _P, _P]),
+        "ac_next_leq_scratch": (_I64, [_I64]),
+        "ac_next_leq_scan": (_I, [_P, _P, _I64, _D, _P, _P, _P]),
+        "ac_window_argmin_f64": (_I, [_P, _P, _I64, _P, _P, _I, _P, _P, _P]),
+        "ac_zero_cross_nearest": (_I, [_P, _P, _I64, _P, _I, _I, _P, _P]),
+        "ac_quiet_guard_slow": (_I, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P]),
+        "ac_pause_cut_points": (_I, [_P, _P, _I64, _P, _P, _I, _I, _I, _P, _P, _P]),
+        "ac_mdx_stft": (_I, [_P, _P, _I64, _P, _P, _P, _I, _P, _P, _P]),
+        "ac_mdx_istft": (_I, [_P, _P, _I, _P, _P, _P]),
+        "ac_mdx_assemble_ola": (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+        "ac_mdx_chunk_vocal": (_I, [_P, _P, _P, _P, _P, _I, _P, _P]),
+        "ac_sum_squares": (_I, [_P, _P, _I64, _P, _I, _P]),
+        "ac_window_sum_squares": (_I, [_P, _P, _I64, _P, _P, _I, _P, _P]),
+        "ac_conv3x3_f16x3": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+        "ac_conv3x3_f16x3_w96": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+        "ac_conv3x3_f16x3_s8": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P]),
+        "ac_conv3x3_f16x3_first": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _F, _F, _P, _P]),
+        "ac_tdf_linear_f16x3": (_I, [_P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _F, _P, _P, _P]),
+        "ac_tdf_small_fused": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _P, _P]),
+        "ac_conv1x1_small": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I64, _I, _P]),
+        "ac_down2x_f16x3": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+        "ac_up2x_f16x3": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+        "ac_pyin_observe": (_I, [_P, _P, _I64, _I, _I, _D, _D, _I, _I, _P, _P, _P, _P, _P, _D, _D, _P, _P, _P, _P]),
+        "ac_pyin_viterbi": (_I, [_P, _P, _P, _I64, _I, _I, _P, _P, _D, _P, _P, _P, _P]),
+        "ac_lpc_formants": (_I, [_P, _P, _I64, _I, _I, _I, _F, _P, _P, _I64, _P]),
+        "ac_zero_crossing_rate": (_I, [_P, _P, _I64, _I, _I, _P, _I64, _P]),
+        "ac_stft2048_spectral": (_I, [_P, _P, _I64, _I, _D, _P, _P, _I64, _P]),
+        "ac_segment_frame_rms": (_I, [_P, _P, _I64, _P, _P, _P, _I, _I, _I, _I, _P, _I64, _P]),
+        "ac_segment_sumsq_peak": (_I, [_P, _P, _I64, _P, _P, _I, _P, _P, _P]),
+        "ac_local_valley_tiles": (_I, [_I, _I]),
+        "ac_local_valley": (_I, [_P, _P, _I64, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+        "ac_resample_poly": (_I, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
+        "ac_pack_pcm24": (_I, [_P, _P, _I64, _P, _P]),
+        "ac_resample_poly_segments": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
+        "ac_silero_frontend": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+        "ac_silero_lstm": (_I, [_P, _P, _P, _P, _I, _P, _P, _P]),
+        "ac_silero_out": (_I, [_P, _P, _P, _F, _I, _P, _P]),
+        "ac_host_beat_dp": (_I, [_P, _I64, _D, _D, _P, _P]),
+    }),
+    # include/audiocut_hip_stereo.h: the true-stereo extension
+    AbiSurface("audiocut_hip_stereo.h", "ac_stereo_abi_version", 1, {
+        "ac_stereo_abi_version": (_I, []),
+        "ac_mdx_stft_stereo": (_I, [_P, _P, _I64, _P, _P, _P, _I, _P, _P, _P]),
+        "ac_mdx_assemble_ola_stereo": (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+        "ac_mdx_chunk_vocal_stereo": (_I, [_P, _P, _I64, _P, _P, _P, _P, _P, _I, _I, _P, _P]),
+    }),
+    # include/audiocut_hip_onset.h: the `librosa_onset` mode's reductions
+    AbiSurface("audiocut_hip_onset.h", "ac_onset_abi_version", 1, {
+        "ac_onset_abi_version": (_I, []),
+        "ac_bar_energy_silence": (_I, [_P, _P, _I64, _P, _P, _I, _D, _P, _P, _P]),
+        "ac_segment_pair_energy": (_I, [_P, _P, _P, _I64, _P, _P, _I, _P, _P]),
+    }),
+    # include/audiocut_hip_beat.h: the beat / bar analysis layer's spectral series and per-bar means
+    AbiSurface("audiocut_hip_beat.h", "ac_beat_abi_version", 1, {
+        "ac_beat_abi_version": (_I, []),
+        "ac_stft2048_centroid_bandwidth": (_I, [_P, _P, _I64, _I, _D, _P, _P, _I64, _P]),
+        "ac_bar_means3": (_I, [_P, _P, _I64, _P, _P, _I64, _P, _P, _I, _P, _P]),
+    }),
+    # include/audiocut_hip_hybrid.h: the `hybrid_mdd` mode's quiet gate
+    AbiSurface("audiocut_hip_hybrid.h", "ac_hybrid_abi_version", 1, {
+        "ac_hybrid_abi_version": (_I, []),
+        "ac_quiet_gate_meansq": (_I, [_P, _P, _I64, _I64, _P, _I, _P, _I64, _P, _P, _P]),
+    }),
+    # include/audiocut_hip_export.h: the `vocal_separation` mode's stem writer
+    AbiSurface("audiocut_hip_export.h", "ac_export_abi_version", 1, {
+        "ac_export_abi_version": (_I, []),
+        "ac_mdx_assemble_pcm24": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+    }),
+    # include/audiocut_hip_asr.h: the `vpbd_asr` mode's 16 kHz 16-bit copy of the vocal stem
+    AbiSurface("audiocut_hip_asr.h", "ac_asr_abi_version", 1, {
+        "ac_asr_abi_version": (_I, []),
+        "ac_resample_poly_pcm16": (_I, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
+    }),
+    # include/audiocut_hip_profile.h: AutoProfile's vocal coverage (peak and count over the resident stem)
+    AbiSurface("audiocut_hip_profile.h", "ac_profile_abi_version", 1, {
+        "ac_profile_abi_version": (_I, []),
+        "ac_abs_peak_coverage": (_I, [_P, _P, _I64, _D, _D, _P, _P, _P, _P]),
+    }),
+    # include/audiocut_hip_final.h: the U-Net's last TDF layer with the final 1x1 conv in its epilogue
+    AbiSurface("audiocut_hip_final.h", "ac_final_abi_version", 1, {
+        "ac_final_abi_version": (_I, []),
+        "ac_tdf_linear_final_f16x3": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, _F, _P, _P]),
+    }),
+    # include/audiocut_hip_load.h: the loader's decode (file bytes -> the resident float32 track)
+    AbiSurface("audiocut_hip_load.h", "ac_load_abi_version", 1, {
+        "ac_load_abi_version": (_I, []),
+        "ac_decode_pcm": (_I, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P, _P]),
+    }),
+    # include/audiocut_hip_pack.h: the export end's sample formats (any of the six WAV subtypes from the resident track or from the
+    # iSTFT waves)
+    AbiSurface("audiocut_hip_pack.h", "ac_pack_abi_version", 1, {
+        "ac_pack_abi_version": (_I, []),
+        "ac_pack_width": (_I, [_I]),
+        "ac_pack_out_align": (_I, [_I]),
+        "ac_pack_pcm": (_I, [_P, _P, _I64, _I, _I64, _I, _P, _P]),
+        "ac_mdx_assemble_pcm": (_I, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+    }),
+    # include/audiocut_hip_rate.h: export at another sample rate (the resident stem -> finished sample bytes of any subtype at
+    # fs * up / down, mono or stereo, one launch).  The wrapper is utils/rate_export.py `resample_pack_device`.
+    AbiSurface("audiocut_hip_rate.h", "ac_rate_abi_version", 1, {
+        "ac_rate_abi_version": (_I, []),
+        "ac_resample_poly_pack": (_I, [_P, _P, _I64, _I, _I64, _I, _I, _P, _I64, _I64, _I, _P, _I64, _P]),
+    }),
+)
+# every export of the library, whichever header declares it
+SIGNATURES = {name: sig for s in ABI_SURFACES for name, sig in s.signatures.items()}
 
-# include/audiocut_hip_export.h: the `vocal_separation` mode's stem writer, exported by the same library and versioned on its own
-EXPORT_SIGNATURES = {
-    "ac_export_abi_version": (C.c_int, []),
-    "ac_mdx_assemble_pcm24": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
-}
-
-# include/audiocut_hip_asr.h: the `vpbd_asr` mode's 16 kHz 16-bit copy of the vocal stem, exported by the same library and versioned
-# on its own
-ASR_SIGNATURES = {
-    "ac_asr_abi_version": (C.c_int, []),
-    "ac_resample_poly_pcm16": (C.c_int, [_P, _P, _I64, _I, _I, _P, _I64, _I64, _P, _I64, _P]),
-}
-
-# include/audiocut_hip_profile.h: AutoProfile's vocal coverage (peak and count over the resident stem), exported by the same library
-# and versioned on its own
-PROFILE_SIGNATURES = {
-    "ac_profile_abi_version": (C.c_int, []),
-    "ac_abs_peak_coverage": (C.c_int, [_P, _P, _I64, C.c_double, C.c_double, _P, _P, _P, _P]),
-}
-# include/audiocut_hip_final.h: the U-Net's last TDF layer with the final 1x1 conv in its epilogue, exported by the same library and
-# versioned on its own
-FINAL_SIGNATURES = {
-    "ac_final_abi_version": (C.c_int, []),
-    "ac_tdf_linear_final_f16x3": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I, _I, _I, _I, _I, C.c_float, _P, _P]),
-}
-# include/audiocut_hip_load.h: the loader's decode (file bytes -> the resident float32 track), exported by the same library and
-# versioned on its own
-LOAD_SIGNATURES = {
-    "ac_load_abi_version": (C.c_int, []),
-    "ac_decode_pcm": (C.c_int, [_P, _P, _I64, _I, _I, _I, _P, _I64, _P, _P]),
-}
-# include/audiocut_hip_pack.h: the export end's sample formats (any of the six WAV subtypes from the resident track or from the iSTFT
-# waves), exported by the same library and versioned on their own
-PACK_SIGNATURES = {
-    "ac_pack_abi_version": (C.c_int, []),
-    "ac_pack_width": (C.c_int, [_I]),
-    "ac_pack_out_align": (C.c_int, [_I]),
-    "ac_pack_pcm": (C.c_int, [_P, _P, _I64, _I, _I64, _I, _P, _P]),
-    "ac_mdx_assemble_pcm": (C.c_int, [_P, _P, _I64, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
-}
-# include/audiocut_hip_rate.h: export at another sample rate (the resident stem -> finished sample bytes of any subtype at
-# fs * up / down, mono or stereo, one launch), exported by the same library and versioned on its own.  The wrapper is
-# utils/rate_export.py `resample_pack_device`.
-RATE_SIGNATURES = {
-    "ac_rate_abi_version": (C.c_int, []),
-    "ac_resample_poly_pack": (C.c_int, [_P, _P, _I64, _I, _I64, _I, _I, _P, _I64, _I64, _I, _P, _I64, _P]),
-}
 # subtype name -> (AC_PACK_* code, bytes per word), and the lookup that refuses every other name: one table for the host conversion,
 # the WAV header and these bindings
 from .utils.audio_export import WAV_SUBTYPES as PACK_SUBTYPES, subtype_info as pack_subtype  # noqa: E402
@@ -222,9 +205,7 @@ def coverage_from(peak: float, count: int, n: int) -> float:
 
 
 def _declare(lib: C.CDLL) -> None:
-    for name, (res, args) in (*SIGNATURES.items(), *STEREO_SIGNATURES.items(), *ONSET_SIGNATURES.items(), *BEAT_SIGNATURES.items(),
-                              *HYBRID_SIGNATURES.items(), *EXPORT_SIGNATURES.items(), *ASR_SIGNATURES.items(), *PROFILE_SIGNATURES.items(),
-                              *FINAL_SIGNATURES.items(), *LOAD_SIGNATURES.items(), *PACK_SIGNATURES.items(), *RATE_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)      # AttributeError here = the .so does not export a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -6,6 +6,17 @@
 #include <vector>
 
 #include "ac_common.h"
+#include "../../include/audiocut_hip_stereo.h"
+#include "../../include/audiocut_hip_onset.h"
+#include "../../include/audiocut_hip_beat.h"
+#include "../../include/audiocut_hip_hybrid.h"
+#include "../../include/audiocut_hip_export.h"
+#include "../../include/audiocut_hip_asr.h"
+#include "../../include/audiocut_hip_profile.h"
+#include "../../include/audiocut_hip_final.h"
+#include "../../include/audiocut_hip_load.h"
+#include "../../include/audiocut_hip_pack.h"
+#include "../../include/audiocut_hip_rate.h"
 
 static thread_local char g_err[512] = "";
 
@@ -17,7 +28,20 @@ void ac_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* ac_last_error(void) { return g_err; }
+
+// ---- the version of every header under include/: one function per header, each header versioned on its own ----
 extern "C" int ac_abi_version(void) { return AC_ABI_VERSION; }
+extern "C" int ac_stereo_abi_version(void) { return AC_STEREO_ABI_VERSION; }
+extern "C" int ac_onset_abi_version(void) { return AC_ONSET_ABI_VERSION; }
+extern "C" int ac_beat_abi_version(void) { return AC_BEAT_ABI_VERSION; }
+extern "C" int ac_hybrid_abi_version(void) { return AC_HYBRID_ABI_VERSION; }
+extern "C" int ac_export_abi_version(void) { return AC_EXPORT_ABI_VERSION; }
+extern "C" int ac_asr_abi_version(void) { return AC_ASR_ABI_VERSION; }
+extern "C" int ac_profile_abi_version(void) { return AC_PROFILE_ABI_VERSION; }
+extern "C" int ac_final_abi_version(void) { return AC_FINAL_ABI_VERSION; }
+extern "C" int ac_load_abi_version(void) { return AC_LOAD_ABI_VERSION; }
+extern "C" int ac_pack_abi_version(void) { return AC_PACK_ABI_VERSION; }
+extern "C" int ac_rate_abi_version(void) { return AC_RATE_ABI_VERSION; }
 
 // ---- Slaney mel scale (librosa.filters.mel(htk=False, norm="slaney"), published algorithm) ----
 static double hz_to_mel(double f) {

@@ -4,8 +4,6 @@
 #include "ac_fft2048.h"
 #include "../../include/audiocut_hip_beat.h"
 
-extern "C" int ac_beat_abi_version(void) { return AC_BEAT_ABI_VERSION; }
-
 // (1) Spectral centroid and bandwidth per frame.  The frame, its FFT, the magnitudes and the centroid are k_stft2048_spectral's
 //     (ac_fft2048.h: the same helpers in the same order, so the centroid has that kernel's bits); the magnitudes stay in LDS for a
 //     third strided sweep, librosa.feature.spectral_bandwidth at p = 2: sqrt(sum_k sn_k * |f_k - centroid|^2), every term >= 0.

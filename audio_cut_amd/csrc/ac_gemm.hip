@@ -361,8 +361,6 @@ extern "C" int ac_tdf_linear_f16x3(ac_ctx* ctx, const float* x, const void* w_pa
     return AC_OK;
 }
 
-extern "C" int ac_final_abi_version(void) { return AC_FINAL_ABI_VERSION; }
-
 extern "C" int ac_tdf_linear_final_f16x3(ac_ctx* ctx, const float* x, const void* w_packed, const float* scale, const float* shift,
                                           const float* resid, const float* final_w, const float* final_b, float* spec, float* y,
                                           long long M, int N, int K, int T, int C, int C_out, float w_unscale, const float* in_amax,

@@ -3,8 +3,6 @@
 #include "ac_common.h"
 #include "../../include/audiocut_hip_hybrid.h"
 
-extern "C" int ac_hybrid_abi_version(void) { return AC_HYBRID_ABI_VERSION; }
-
 // One wave per job, four jobs per workgroup.  Jobs 0 .. n_blocks - 1 are the consecutive blocks, the rest the windows around the
 // centres.  Lane l adds the squares of lo + l, lo + l + 64, ... (a coalesced 256-byte sweep per step) in float64, then the shuffle
 // tree of wave_sum_f64: the order depends on (lo, hi) alone.  [lo, hi) is clamped to [0, n) whatever the centre is.

@@ -15,8 +15,6 @@
 #include "ac_common.h"
 #include "../../include/audiocut_hip_load.h"
 
-extern "C" int ac_load_abi_version(void) { return AC_LOAD_ABI_VERSION; }
-
 #define AC_LOAD_STAGE_BYTES 16384      // >= 256 frames of the widest frame (8 channels x 8 bytes)
 
 template <int FMT> struct ld_width { static constexpr int value = FMT == AC_LOAD_U8 ? 1 : FMT == AC_LOAD_S16 ? 2 : FMT == AC_LOAD_S24 ? 3 : FMT == AC_LOAD_F64 ? 8 : 4; };

@@ -348,10 +348,6 @@ extern "C" int ac_mdx_chunk_vocal_stereo(ac_ctx* ctx, const float* track, int64_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Version of the stereo extension's ABI (include/audiocut_hip_stereo.h); the main header's ac_abi_version() is unchanged.
-extern "C" int ac_stereo_abi_version(void) { return AC_STEREO_ABI_VERSION; }
-
-// ---------------------------------------------------------------------------------------------
 // per-block partial sums of squares in float64 (enhanced_vocal_separator.py:490-501 energy ratios);
 // the host adds the (<= 4096) partials in index order, so the result is deterministic.
 __global__ __launch_bounds__(256) void k_sum_squares(const float* __restrict__ x, int64_t n, double* __restrict__ out) {

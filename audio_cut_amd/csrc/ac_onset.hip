@@ -4,8 +4,6 @@
 #include "ac_common.h"
 #include "../../include/audiocut_hip_onset.h"
 
-extern "C" int ac_onset_abi_version(void) { return AC_ONSET_ABI_VERSION; }
-
 // (1) Blocks [0, n_bars): bar b's mean of rms[lo, hi) - thread t adds frames lo + t, lo + t + 256, ... in float64, then the wave
 //     tree and the fixed sum of the four waves.  Blocks [n_bars, ...): one frame per thread, the silent flag in float64 from
 //     the float32 RMS value (`20 * log10(rms + 1e-10) < threshold_db`, :1148-1149).

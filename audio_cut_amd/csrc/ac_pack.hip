@@ -17,8 +17,6 @@
 #define MDX_TRIM 3072
 #define MDX_GEN 254976
 
-extern "C" int ac_pack_abi_version(void) { return AC_PACK_ABI_VERSION; }
-
 extern "C" int ac_pack_width(int subtype) { return pk_width(subtype); }
 extern "C" int ac_pack_out_align(int subtype) { return pk_align(subtype); }
 
@@ -225,8 +223,6 @@ extern "C" int ac_mdx_assemble_pcm(ac_ctx* ctx, const float* track, int64_t n, i
 }
 
 // ---- the 24-bit entry points: the AC_PACK_PCM_24 instances under their older names ------------------------------------------------
-extern "C" int ac_export_abi_version(void) { return AC_EXPORT_ABI_VERSION; }
-
 // A mono stream of n samples.  The alignment asked of x makes this always k_pack_pcm<1, AC_PACK_PCM_24, true>: a float4 load and
 // three dwords per thread, the last partial group byte by byte.
 extern "C" int ac_pack_pcm24(ac_ctx* ctx, const float* x, int64_t n, unsigned char* out, void* stream) {

@@ -15,8 +15,6 @@
 #include "ac_common.h"
 #include "../../include/audiocut_hip_asr.h"
 
-extern "C" int ac_asr_abi_version(void) { return AC_ASR_ABI_VERSION; }
-
 // What ac_resample_poly and ac_resample_poly_pcm16 ask of their sizes, and the grid: four waves per workgroup, AC_RS_PER_WAVE
 // outputs per wave.
 static int rs_check_sizes(int64_t n, int up, int down, int64_t hlen, int64_t n_pre_remove, int64_t n_out, int64_t* n_blocks) {

@@ -3,8 +3,6 @@
 #include "ac_common.h"
 #include "../../include/audiocut_hip_profile.h"
 
-extern "C" int ac_profile_abi_version(void) { return AC_PROFILE_ABI_VERSION; }
-
 // Magnitude bits of a float: for finite values they order exactly as |x| does (+-0 -> 0, denormals included), so the maximum and
 // the comparison below are integer operations and do not depend on the float denormal mode.
 __device__ inline unsigned pf_mag(float v) { return __float_as_uint(v) & 0x7fffffffu; }

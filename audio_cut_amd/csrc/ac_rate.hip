@@ -9,8 +9,6 @@
 #include "../../include/audiocut_hip_rate.h"
 #include "ac_pack_words.h"
 
-extern "C" int ac_rate_abi_version(void) { return AC_RATE_ABI_VERSION; }
-
 // A wave owns AC_RS_PER_WAVE = 8 consecutive words of the output stream, words w0 .. w0 + 7 with w0 % 8 == 0: eight mono samples,
 // or four stereo frames L, R, L, R, .. (word w is channel w & 1 of frame w >> 1, and w & 1 == j & 1).  They are two groups of
 // ac_store_pcm_group.  Every lane holds every sum (butterfly reduction), so lane 0 has both groups in registers and stores them:

@@ -1,35 +1,17 @@
-"""C-ABI library loads and exports every symbol include/audiocut_hip.h declares; host-side logic of the
-product (no GPU compute).  CPU only."""
+"""Host-side entry points of the C-ABI library (size queries, error codes, the beat DP) and host-side logic of the product (no GPU
+compute); the built library's device code is free of the instructions it must not contain.  The ABI surface itself is held by
+tests/test_abi_surfaces.py.  CPU only."""
 import ctypes
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+from abi_surface import lib  # noqa: F401  (the fixture)
+
 ROOT = Path(__file__).resolve().parent.parent
 SR = 44100
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_header_symbols_exported(lib):
-    header = (ROOT / "include" / "audiocut_hip.h").read_text()
-    names = sorted(set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", header)))
-    assert len(names) >= 20
-    from audio_cut_amd import _native
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the header but not exported"
-        assert name in _native.SIGNATURES, f"{name} has no ctypes signature"
-    assert set(_native.SIGNATURES) == set(names)
-    assert lib.ac_abi_version() == 6
 
 
 def test_size_helpers_need_no_gpu(lib):
@@ -398,72 +380,3 @@ def test_resampling_filter_meets_the_soxr_hq_specification():
     x = np.random.default_rng(0).standard_normal(3000).astype(np.float32)
     assert ORS.resample(x, 16000, 44100).shape == (-(-3000 * 160 // 441),)          # librosa / resample_poly length rule
     assert np.array_equal(ORS.resample(x, 5, 5), x)
-
-
-# every export of include/audiocut_hip.h -> the GPU test that calls it directly and compares it with a reference ("module::test"), or
-# "host-only" (context and error plumbing, size queries, the host C++ beat DP: tested on the CPU above)
-EXPORT_TESTS = {
-    "ac_abi_version": "host-only",
-    "ac_last_error": "host-only",
-    "ac_ctx_create": "host-only",
-    "ac_ctx_destroy": "host-only",
-    "ac_next_leq_scratch": "host-only",
-    "ac_tempogram_parts": "host-only",
-    "ac_local_valley_tiles": "host-only",
-    "ac_host_beat_dp": "host-only",
-    "ac_frame_rms": "test_kernels_gpu::test_frame_rms",
-    "ac_frame_rms_multi": "test_kernels_gpu::test_frame_rms_multi_is_the_single_kernel_bit_for_bit",
-    "ac_stft2048_features": "test_kernels_gpu::test_stft_flatness_and_mel",
-    "ac_onset_strength": "test_kernels_gpu::test_onset_strength",
-    "ac_tempogram_reduce": "test_kernels_gpu::test_tempogram_reduce",
-    "ac_yin_f0": "test_kernels_gpu::test_yin_f0_autocorrelation_kernel",
-    "ac_moving_meansq_db_f64": "test_cut_refine_edges_gpu::test_moving_meansq_db_edges",
-    "ac_next_leq_scan": "test_cut_refine_edges_gpu::test_next_leq_scan_edges",
-    "ac_window_argmin_f64": "test_cut_refine_edges_gpu::test_window_argmin_edges",
-    "ac_zero_cross_nearest": "test_cut_refine_edges_gpu::test_zero_cross_nearest_edges",
-    "ac_quiet_guard_slow": "test_cut_refine_edges_gpu::test_quiet_guard_slow_edges",
-    "ac_pause_cut_points": "test_cut_refine_edges_gpu::test_pause_cut_points_edges",
-    "ac_mdx_stft": "test_mdx_kernels_gpu::test_stft_against_float64",
-    "ac_mdx_istft": "test_mdx_kernels_gpu::test_istft_against_float64",
-    "ac_mdx_assemble_ola": "test_mdx_kernels_gpu::test_assemble_ola_exact_over_plans",
-    "ac_mdx_chunk_vocal": "test_kernels_edges_gpu::test_mdx_chunk_vocal_edges",
-    "ac_sum_squares": "test_kernels_edges_gpu::test_mean_square_partials_edges",
-    "ac_window_sum_squares": "test_kernels_gpu::test_window_mean_squares_is_the_per_window_mean_square_bit_for_bit",
-    "ac_conv3x3_f16x3": "test_unet_gpu::test_conv3x3_f16x3_kernel",
-    "ac_conv3x3_f16x3_w96": "test_unet_gpu::test_conv3x3_f16x3_w96_kernel",
-    "ac_conv3x3_f16x3_s8": "test_kernels_edges_gpu::test_level0_conv_at_64_items_matches_2_items",
-    "ac_conv3x3_f16x3_first": "test_unet_gpu::test_first_conv_fused_into_the_3x3_loader_is_bit_identical",
-    "ac_conv1x1_small": "test_unet_gpu::test_conv1x1_small_kernel",
-    "ac_tdf_linear_f16x3": "test_unet_gpu::test_tdf_linear_f16x3_kernel",
-    "ac_tdf_small_fused": "test_unet_gpu::test_tdf_small_fused_kernel",
-    "ac_down2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
-    "ac_up2x_f16x3": "test_unet_gpu::test_fused_resampling_kernels_vs_float64",
-    "ac_pyin_observe": "test_pitch_kernels_gpu::test_observe_crafted_rows",
-    "ac_pyin_viterbi": "test_pitch_kernels_gpu::test_viterbi_bit_exact",
-    "ac_lpc_formants": "test_pitch_kernels_gpu::test_lpc_formants_exact",
-    "ac_zero_crossing_rate": "test_kernels_edges_gpu::test_zero_crossing_rate_edges",
-    "ac_stft2048_spectral": "test_kernels_edges_gpu::test_stft2048_spectral_edges",
-    "ac_segment_frame_rms": "test_kernels_edges_gpu::test_segment_frame_rms_edges",
-    "ac_segment_sumsq_peak": "test_kernels_edges_gpu::test_segment_sumsq_peak_edges",
-    "ac_local_valley": "test_kernels_edges_gpu::test_local_valley_edges",
-    "ac_resample_poly": "test_resample_pcm_edges_gpu::test_resample_poly_same_taps",
-    "ac_resample_poly_segments": "test_kernels_edges_gpu::test_resample_poly_segments_edges",
-    "ac_pack_pcm24": "test_resample_pcm_edges_gpu::test_pack_pcm24_known_answers_in_every_lane_and_in_the_tail",
-    "ac_silero_frontend": "test_silero_kernels_gpu::test_frontend_against_float64",
-    "ac_silero_lstm": "test_silero_kernels_gpu::test_lstm_synthetic_gates",
-    "ac_silero_out": "test_silero_kernels_gpu::test_out_against_float64",
-}
-
-
-def test_every_export_names_its_direct_test():
-    """A new export fails here until someone names the GPU test that calls it directly and compares it with a reference."""
-    import ast
-    header = (ROOT / "include" / "audiocut_hip.h").read_text()
-    assert set(EXPORT_TESTS) == set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", header))
-    defined = {}
-    for ref in set(EXPORT_TESTS.values()) - {"host-only"}:
-        module, name = ref.split("::")
-        if module not in defined:
-            tree = ast.parse((ROOT / "tests" / f"{module}.py").read_text())
-            defined[module] = {node.name for node in tree.body if isinstance(node, ast.FunctionDef)}
-        assert name in defined[module], f"{ref} does not exist"

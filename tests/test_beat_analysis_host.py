@@ -1,27 +1,19 @@
 """Host side of the beat / bar analysis layer: both branches of `detect_chorus_regions` against the reference's recorded
-results (tests/golden/beat_analysis.npz), the bar boundary and frame-range construction against boolean masks, and the ABI of
-include/audiocut_hip_beat.h (exported, bound, versioned on its own, bad arguments refused).  CPU only."""
-import ast
+results (tests/golden/beat_analysis.npz), the bar boundary and frame-range construction against boolean masks, and the bad
+arguments the entry points of include/audiocut_hip_beat.h refuse.  CPU only."""
 import json
 import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd.analysis import beat_analyzer as BA
 from audio_cut_amd.analysis import chorus_regions as CR
 from audio_cut_amd.testing import beat_cases
 
 ROOT = Path(__file__).resolve().parent.parent
-
-# every export of include/audiocut_hip_beat.h -> the GPU test that calls it directly and compares it with a reference, or "host-only"
-BEAT_EXPORT_TESTS = {
-    "ac_beat_abi_version": "host-only",
-    "ac_stft2048_centroid_bandwidth": "test_beat_analysis_gpu::test_centroid_bandwidth_against_librosa",
-    "ac_bar_means3": "test_beat_analysis_gpu::test_bar_means3_against_numpy",
-}
 
 
 @pytest.fixture(scope="module")
@@ -204,45 +196,6 @@ def test_result_counts_and_mono():
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_beat_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_beat.h")
-    assert names == set(_native.BEAT_SIGNATURES)
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the beat header but not exported"
-    assert lib.ac_beat_abi_version() == 1
-    # argument counts of the prototypes against the ctypes tables
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_beat.h").read_text(), flags=re.S)
-    for name, args in re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.BEAT_SIGNATURES[name][1]), name
-    # the other headers' surfaces are untouched
-    main = _names("audiocut_hip.h")
-    assert main == set(_native.SIGNATURES) and not (main & names) and len(main) == 49
-    assert lib.ac_abi_version() == 6 and lib.ac_stereo_abi_version() == 1 and lib.ac_onset_abi_version() == 1
-    assert not (names & (_names("audiocut_hip_stereo.h") | _names("audiocut_hip_onset.h")))
-
-
-def test_every_beat_export_names_its_direct_test():
-    assert set(BEAT_EXPORT_TESTS) == _names("audiocut_hip_beat.h")
-    for ref in set(BEAT_EXPORT_TESTS.values()) - {"host-only"}:
-        module, name = ref.split("::")
-        tree = ast.parse((ROOT / "tests" / f"{module}.py").read_text())
-        assert name in {node.name for node in tree.body if isinstance(node, ast.FunctionDef)}, f"{ref} does not exist"
-
-
 def test_beat_entry_points_reject_bad_arguments(lib):
     # null context / sizes out of range come back as AC_E_INVALID, never as a launch
     assert lib.ac_stft2048_centroid_bandwidth(None, None, 0, 0, 44100.0, None, None, 0, None) == -1

@@ -1,20 +1,19 @@
 """Host side of the export subtypes (`output.wav.subtype`): the conversion of `pcm_bytes_host` against known answers derived from
 its definition, `export_audio` round trips through `wav_reader`, the refusal of every other subtype, the bytes of PCM_16 and PCM_24
-files pinned by hash, the configuration keys, and the ABI of include/audiocut_hip_pack.h.  CPU only; every comparison is exact."""
+files pinned by hash, the configuration keys, and the subtype table and refusals of include/audiocut_hip_pack.h.  CPU only; every comparison is exact."""
 import ctypes as C
 import hashlib
 import re
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd.utils import audio_export as AE
 from audio_cut_amd.utils import wav_reader as WR
 
-ROOT = Path(__file__).resolve().parent.parent
 SR = 44100
 SUBTYPES = ("PCM_U8", "PCM_16", "PCM_24", "PCM_32", "FLOAT", "DOUBLE")
 WIDTH = {"PCM_U8": 1, "PCM_16": 2, "PCM_24": 3, "PCM_32": 4, "FLOAT": 4, "DOUBLE": 8}
@@ -233,48 +232,15 @@ def test_api_refuses_the_format_before_any_work(tmp_path):
     assert not list((tmp_path / "out").iterdir())
 
 
-# ---- the ABI of include/audiocut_hip_pack.h ---------------------------------------------------------------------------------------
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
+# ---- include/audiocut_hip_pack.h --------------------------------------------------------------------------------------------------
+def test_subtype_table_is_the_headers_the_librarys_and_the_hosts(lib):
     from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_pack_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_pack.h")
-    declared = {"ac_pack_abi_version", "ac_pack_width", "ac_pack_out_align", "ac_pack_pcm", "ac_mdx_assemble_pcm"}
-    assert names == set(_native.PACK_SIGNATURES) == declared
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in the pack header but not exported"
-    assert lib.ac_pack_abi_version() == 1
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_pack.h").read_text(), flags=re.S)
-    assert "#define AC_PACK_ABI_VERSION 1" in text
-    found = re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
-    assert {name for name, _ in found} == declared
-    for name, args in found:
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.PACK_SIGNATURES[name][1]), name
-    # the other surfaces are untouched, and this one shares no name with them
-    main = _names("audiocut_hip.h")
-    assert main == set(_native.SIGNATURES) and not (main & declared)
-    assert set(_native.EXPORT_SIGNATURES) == {"ac_export_abi_version", "ac_mdx_assemble_pcm24"} and lib.ac_export_abi_version() == 1
-    assert lib.ac_abi_version() == 6 and lib.ac_load_abi_version() == 1
-    # the subtype table is the header's, the library's and the host's
-    codes = dict(re.findall(r"#define AC_PACK_(PCM_U8|PCM_16|PCM_24|PCM_32|FLOAT|DOUBLE) (\d)", text))
+    codes = dict(re.findall(r"#define AC_PACK_(PCM_U8|PCM_16|PCM_24|PCM_32|FLOAT|DOUBLE) (\d)", abi_surface.code("audiocut_hip_pack.h")))
     assert {k: (int(v), WIDTH[k]) for k, v in codes.items()} == AE.WAV_SUBTYPES == _native.PACK_SUBTYPES
     for name, (code, width) in AE.WAV_SUBTYPES.items():
         assert lib.ac_pack_width(code) == width
         assert lib.ac_pack_out_align(code) == {1: 4, 2: 8, 3: 4, 4: 16, 8: 16}[width]
     assert lib.ac_pack_width(6) == lib.ac_pack_width(-1) == lib.ac_pack_out_align(6) == 0
-    mk = (ROOT / "audio_cut_amd" / "csrc" / "Makefile").read_text()
-    assert "ac_pack.hip" in mk and "audiocut_hip_pack.h" in mk
 
 
 def test_pack_entry_points_reject_bad_arguments(lib):

@@ -1,20 +1,17 @@
 """Host side of mode `hybrid_mdd`: both strategies, `deduplicate_and_convert_cuts`, the flag remap, the micro-merge and the
 config against the reference's recorded results (tests/golden/hybrid_mdd.npz, the gate's answers taken from the fixture), and the
-ABI of include/audiocut_hip_hybrid.h (exported, bound, versioned on its own, bad arguments refused).  CPU only."""
+bad arguments the entry point of include/audiocut_hip_hybrid.h refuses.  CPU only."""
 import ctypes as C
 import json
-import re
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd import config as cfg
 from audio_cut_amd.cutting import hybrid_strategies as HS
 from audio_cut_amd.testing import hybrid_cases
 
-ROOT = Path(__file__).resolve().parent.parent
 SR = hybrid_cases.SR
 NAMES = [c["name"] for c in hybrid_cases.CASES]
 
@@ -169,35 +166,6 @@ def test_mode_is_listed_and_fixture_covers_what_it_must(golden):
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------------
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_hybrid_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_hybrid.h")
-    assert names == set(_native.HYBRID_SIGNATURES) == {"ac_hybrid_abi_version", "ac_quiet_gate_meansq"}
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the hybrid header but not exported"
-    assert lib.ac_hybrid_abi_version() == 1
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_hybrid.h").read_text(), flags=re.S)
-    for name, args in re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.HYBRID_SIGNATURES[name][1]), name
-    main = _names("audiocut_hip.h")                                    # the other surfaces are untouched
-    assert main == set(_native.SIGNATURES) and not (main & names)
-    assert lib.ac_abi_version() == 6 and lib.ac_beat_abi_version() == 1
-    assert not (names & (_names("audiocut_hip_stereo.h") | _names("audiocut_hip_onset.h") | _names("audiocut_hip_beat.h")))
-
-
 def test_quiet_gate_rejects_bad_arguments(lib):
     """Every refusal comes back as AC_E_INVALID with a message, before anything is launched; the empty call is a no-op.  The context
     handle is never read by the checks, so a placeholder stands in for one here (no device on this machine)."""

@@ -1,23 +1,20 @@
 """`output.sample_rate` on the host (audio_cut_amd/utils/rate_export.py): how the setting resolves and what it refuses, the cut
 mapping, the host statement of the resampled bytes against scipy.signal.resample_poly with the same taps, the lossless round trip
-of a file's own data chunk, and the ABI surface of include/audiocut_hip_rate.h.  CPU only."""
+of a file's own data chunk, and the bad arguments the entry point of include/audiocut_hip_rate.h refuses.  CPU only."""
 import ctypes as C
-import re
 import struct
-import subprocess
 import wave
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import resample_refs as R
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd import _native, api, config
 from audio_cut_amd.utils import audio_export as AE
 from audio_cut_amd.utils import rate_export as RE
 from audio_cut_amd.utils import wav_reader as WR
 
-ROOT = Path(__file__).resolve().parent.parent
 SR = 44100
 
 
@@ -259,46 +256,7 @@ def test_manifest_export_block_only_with_the_setting(tmp_path):
     assert man["audio"]["sr"] == SR and man["cuts"]["samples"] == [0, 64]
 
 
-# ---- the ABI of include/audiocut_hip_rate.h ------------------------------------------------------------------------------------------
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_rate_header_symbols_exported_and_bound(lib):
-    names = _names("audiocut_hip_rate.h")
-    declared = {"ac_rate_abi_version", "ac_resample_poly_pack"}
-    assert names == set(_native.RATE_SIGNATURES) == declared
-    for name in declared:
-        assert hasattr(lib, name), f"{name} declared in the rate header but not exported"
-    assert lib.ac_rate_abi_version() == 1
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_rate.h").read_text(), flags=re.S)
-    assert "#define AC_RATE_ABI_VERSION 1" in text
-    found = re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
-    assert {name for name, _ in found} == declared
-    for name, args in found:
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.RATE_SIGNATURES[name][1]), name
-    # the other surfaces are untouched, and this one shares no name with them
-    main = _names("audiocut_hip.h")
-    assert main == set(_native.SIGNATURES) and not (main & declared)
-    others = sorted(p.name for p in (ROOT / "include").glob("audiocut_hip_*.h") if p.name != "audiocut_hip_rate.h")
-    assert len(others) == 10
-    for other in others:
-        assert not (declared & _names(other)), other
-    assert lib.ac_abi_version() == 6 and lib.ac_pack_abi_version() == 1 and lib.ac_asr_abi_version() == 1 and lib.ac_load_abi_version() == 1
-    assert set(_native.PACK_SIGNATURES) == {"ac_pack_abi_version", "ac_pack_width", "ac_pack_out_align", "ac_pack_pcm", "ac_mdx_assemble_pcm"}
-    assert set(_native.ASR_SIGNATURES) == {"ac_asr_abi_version", "ac_resample_poly_pcm16"}
-    mk = (ROOT / "audio_cut_amd" / "csrc" / "Makefile").read_text()
-    assert "ac_rate.hip" in mk and "audiocut_hip_rate.h" in mk and "ac_pack_words.h" in mk
-
-
+# ---- include/audiocut_hip_rate.h -------------------------------------------------------------------------------------------------------
 def test_rate_entry_point_rejects_bad_arguments(lib):
     """Every refusal comes back as AC_E_INVALID with a message, before anything is launched.  The checks never read the context or
     the buffers, so placeholders stand in for them here (no device on this machine)."""

@@ -1,28 +1,19 @@
 """Mode `librosa_onset` without a GPU: the pure host rules of audio_cut_amd/cutting/smart_segment.py against the reference's
 recorded results (tests/golden/librosa_onset.npz, written by tests/golden/make_onset_golden.py), the mode's configuration,
-and the ABI of include/audiocut_hip_onset.h (exported, bound, versioned on its own, bad arguments refused)."""
-import ast
+and the bad arguments the entry points of include/audiocut_hip_onset.h refuse."""
 import json
-import re
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd import config as cfg
 from audio_cut_amd.cutting import smart_segment as SS
 
 ROOT = Path(__file__).resolve().parent.parent
 SR = 44100
 TYPE_NAME = {0: "verse", 1: "chorus", 2: "chorus_peak"}
-
-# every export of include/audiocut_hip_onset.h -> the GPU test that calls it directly and compares it with a reference, or "host-only"
-ONSET_EXPORT_TESTS = {
-    "ac_onset_abi_version": "host-only",
-    "ac_bar_energy_silence": "test_smart_segment_gpu::test_bar_energy_silence_against_numpy",
-    "ac_segment_pair_energy": "test_smart_segment_gpu::test_segment_pair_energy_against_numpy",
-}
 
 
 @pytest.fixture(scope="module")
@@ -155,40 +146,6 @@ def test_mode_is_supported_and_failure_builds_a_manifest(tmp_path):
 
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_onset_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_onset.h")
-    assert names == set(_native.ONSET_SIGNATURES)
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the onset header but not exported"
-    assert lib.ac_onset_abi_version() == 1
-    # the other two headers' surfaces are untouched and disjoint from this one
-    main, stereo = _names("audiocut_hip.h"), _names("audiocut_hip_stereo.h")
-    assert main == set(_native.SIGNATURES) and stereo == set(_native.STEREO_SIGNATURES)
-    assert not (names & main) and not (names & stereo)
-    assert lib.ac_abi_version() == 6 and lib.ac_stereo_abi_version() == 1
-
-
-def test_every_onset_export_names_its_direct_test():
-    assert set(ONSET_EXPORT_TESTS) == _names("audiocut_hip_onset.h")
-    for ref in set(ONSET_EXPORT_TESTS.values()) - {"host-only"}:
-        module, name = ref.split("::")
-        tree = ast.parse((ROOT / "tests" / f"{module}.py").read_text())
-        assert name in {node.name for node in tree.body if isinstance(node, ast.FunctionDef)}, f"{ref} does not exist"
-
-
 def test_onset_entry_points_reject_bad_arguments(lib):
     # null pointers / zero sizes come back as AC_E_INVALID with a message, never as a launch or an exception
     import ctypes as C

@@ -1,43 +1,8 @@
-"""include/audiocut_hip_final.h: the header, the exports and the ctypes signatures agree, the other ABI surfaces are untouched, and
-every precondition of ac_tdf_linear_final_f16x3 is refused on the host before anything is launched.  CPU only."""
+"""include/audiocut_hip_final.h: every precondition of ac_tdf_linear_final_f16x3 is refused on the host before anything is
+launched, and `Context.tdf_final_tileable` states the same conditions.  CPU only."""
 import ctypes as C
-import re
-import subprocess
-from pathlib import Path
 
-import pytest
-
-ROOT = Path(__file__).resolve().parent.parent
-
-
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_final_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_final.h")
-    assert names == set(_native.FINAL_SIGNATURES) == {"ac_final_abi_version", "ac_tdf_linear_final_f16x3"}
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the final-layer header but not exported"
-    assert lib.ac_final_abi_version() == 1
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_final.h").read_text(), flags=re.S)
-    for name, args in re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.FINAL_SIGNATURES[name][1]), name
-    main = _names("audiocut_hip.h")                                    # the other surfaces are untouched
-    assert main == set(_native.SIGNATURES) and not (main & names)
-    assert lib.ac_abi_version() == 6 and lib.ac_profile_abi_version() == 1
-    others = ("stereo", "onset", "beat", "hybrid", "export", "asr", "profile")
-    assert not any(names & _names(f"audiocut_hip_{o}.h") for o in others)
+from abi_surface import lib  # noqa: F401  (the fixture)
 
 
 def test_final_entry_refuses_every_shape_outside_its_tile(lib):

@@ -1,18 +1,18 @@
-"""The RIFF/WAVE reader (audio_cut_amd/utils/wav_reader.py), the host loaders built on it, and the ABI surface of
-include/audiocut_hip_load.h.  CPU only: files are built with `struct`, every comparison is exact."""
+"""The RIFF/WAVE reader (audio_cut_amd/utils/wav_reader.py), the host loaders built on it, and the constants and refusals
+of include/audiocut_hip_load.h.  CPU only: files are built with `struct`, every comparison is exact."""
 import ctypes as C
 import re
 import struct
-import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import abi_surface
+from abi_surface import lib  # noqa: F401  (the fixture)
 from audio_cut_amd.utils import wav_reader as WR
 from audio_cut_amd.utils.wav_reader import UnsupportedAudioError
 
-ROOT = Path(__file__).resolve().parent.parent
 KS_TAIL = bytes.fromhex("000000001000800000AA00389B71")
 
 
@@ -281,42 +281,12 @@ def test_manifest_duration_comes_from_the_reader(tmp_path):
 
 # ---- ABI ---------------------------------------------------------------------------------------------------------------------------
 
-def _names(header: str) -> set:
-    return set(re.findall(r"\b(ac_[a-z0-9_]+)\s*\(", (ROOT / "include" / header).read_text()))
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from audio_cut_amd import _native
-    if not _native.library_path().exists():
-        subprocess.run(["make", "-C", str(ROOT / "audio_cut_amd" / "csrc")], check=True)
-    return _native.load()
-
-
-def test_load_header_symbols_exported_and_bound(lib):
-    from audio_cut_amd import _native
-    names = _names("audiocut_hip_load.h")
-    assert names == set(_native.LOAD_SIGNATURES) == {"ac_load_abi_version", "ac_decode_pcm"}
-    for name in names:
-        assert hasattr(lib, name), f"{name} declared in the loader header but not exported"
-    assert lib.ac_load_abi_version() == 1
-    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "audiocut_hip_load.h").read_text(), flags=re.S)
-    for name, args in re.findall(r"\bint\s+(ac_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        n_args = 0 if args.strip() == "void" else len(args.split(","))
-        assert n_args == len(_native.LOAD_SIGNATURES[name][1]), name
-    main = _names("audiocut_hip.h")                                    # the other surfaces are untouched
-    assert main == set(_native.SIGNATURES) and not (main & names)
-    assert lib.ac_abi_version() == 6 and lib.ac_final_abi_version() == 1 and lib.ac_profile_abi_version() == 1
-    others = ("stereo", "onset", "beat", "hybrid", "export", "asr", "profile", "final")
-    assert not any(names & _names(f"audiocut_hip_{o}.h") for o in others)
-    # the header's constants and the reader's tables are one numbering
-    consts = dict(re.findall(r"#define\s+(AC_LOAD_[A-Z0-9_]+)\s+(\d+)", text))
+def test_load_header_constants_and_the_readers_tables_are_one_numbering():
+    consts = dict(re.findall(r"#define\s+(AC_LOAD_[A-Z0-9_]+)\s+(\d+)", abi_surface.code("audiocut_hip_load.h")))
     assert {k: WR.SAMPLE_FORMATS[k][0] for k in WR.SAMPLE_FORMATS} == {k.split("_")[-1].lower(): int(v) for k, v in consts.items()
                                                                       if k.split("_")[-1].lower() in WR.SAMPLE_FORMATS}
     assert (int(consts["AC_LOAD_MONO"]), int(consts["AC_LOAD_PLANAR"])) == (WR.LAYOUT_MONO, WR.LAYOUT_PLANAR)
-    assert int(consts["AC_LOAD_MAX_CHANNELS"]) == WR.MAX_CHANNELS and int(consts["AC_LOAD_ABI_VERSION"]) == 1
-    mk = (ROOT / "audio_cut_amd" / "csrc" / "Makefile").read_text()
-    assert "ac_load.hip" in mk and "audiocut_hip_load.h" in mk
+    assert int(consts["AC_LOAD_MAX_CHANNELS"]) == WR.MAX_CHANNELS
 
 
 def test_decode_entry_refuses_before_anything_is_launched(lib):
