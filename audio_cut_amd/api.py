@@ -285,6 +285,28 @@ def last_result() -> Optional[Dict[str, Any]]:
     return _LAST_RESULT
 
 
+# the segment-finishing keys of `quality_control` and their defaults (config/__init__.py): with all five there, nothing of the feature
+# is imported and the finish library is not opened
+_FINISH_DEFAULTS = {"fade_in_duration": 0.0, "fade_out_duration": 0.0, "normalize_audio": False, "normalize_target_db": -20.0,
+                    "normalize_max_gain": 10.0}
+
+
+def _configured_finish(sr: int):
+    """The `FinishSettings` of an export whose segments are to be faded or normalised, else None.  A key off its default is read -
+    and refused by name if it cannot be honoured - before any work."""
+    if all(_config.get_config(f"quality_control.{k}", d) in (d, None) for k, d in _FINISH_DEFAULTS.items()):
+        return None
+    from .utils.segment_finish import configured_finish
+    settings = configured_finish(sr)
+    return settings if settings.active else None
+
+
+def _finish_keys_in_force(finish) -> list:
+    return [f"quality_control.{k}" for k, on in (("fade_in_duration", finish.fade_in_frames > 0),
+                                                 ("fade_out_duration", finish.fade_out_frames > 0),
+                                                 ("normalize_audio", finish.normalize_audio)) if on]
+
+
 def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Optional[Sequence[str]], sr: int,
                       device: Optional[str], channels: int = 1) -> Dict[str, Any]:
     """The reference's `split_audio_seamlessly` for the modes built here (`seamless_splitter.py:171-253,270-760`): load,
@@ -294,6 +316,7 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter, configured_subtype
     t_start = time.time()
     subtype = configured_subtype()          # `output.format` / `output.wav.subtype`: refused here, before any work, if not written
+    finish = _configured_finish(sr)         # segment finishing (utils/segment_finish.py); None with the keys at their defaults
     # `output.sample_rate` (utils/rate_export.py): the rate the files leave at, resolved - and refused - from the file's header
     # alone, before the track is loaded.  Absent: `out_sr` is `sr` and nothing below differs from a build without the setting.
     rate_set = _config.get_config("output.sample_rate", None) is not None
@@ -305,6 +328,10 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
             raise ValueError(f"output.sample_rate {out_sr} with mode 'vocal_separation': that mode writes its bytes straight from the "
                              f"iSTFT and has no float stem to resample, so it exports at audio.sample_rate ({sr}) only; mode "
                              f"'v2.2_mdd' with export_types=[\"full_vocal\", \"full_instrumental\"] writes the same two files at {out_sr} Hz")
+        if finish is not None and out_sr != sr:
+            raise ValueError(f"{', '.join(_finish_keys_in_force(finish))} with output.sample_rate {out_sr}: segments are finished at "
+                             f"audio.sample_rate ({sr}) only, the resampling export does not know where the segments are; leave "
+                             f"output.sample_rate unset (or at {sr}), or the finishing keys at their defaults")
     splitter = SeamlessSplitter(sample_rate=sr, device=device)
     hip = splitter._context()
     audio_dev = None
@@ -379,7 +406,9 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         def packed(track, dev):
             return PackedTrack.resampled(track, sr, out_sr, n_out, subtype, hip=hip, dev=dev)
     if "mix_segments" in plan:
-        if source_track is not None:        # the loaded track as it was in front of the load resampler: nothing is resampled twice
+        if finish is not None:              # out_sr == sr here: the spans are finished where the track becomes bytes
+            mix_pk = PackedTrack.finished(audio, sr, spans, finish, subtype, hip=hip, dev=mix_dev)
+        elif source_track is not None:      # the loaded track as it was in front of the load resampler: nothing is resampled twice
             is_dev = not isinstance(source_track, np.ndarray)
             mix_pk = PackedTrack(source_track, out_sr, subtype, hip=hip, dev=source_track if is_dev else None)
         else:
@@ -388,9 +417,14 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
                                                       **naming)
         exp.saved_files += exp.mix_segment_files
     vocal = res.get("vocal_track" + st)
-    voc_pk = packed(vocal, state.get("vocal" + st)) if (vocal is not None and ("vocal_segments" in plan or "full_vocal" in plan)) else None
-    if "vocal_segments" in plan and voc_pk is not None:
-        exp.vocal_segment_files = exporter.export_spans(voc_pk, out_spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
+    # finishing: the full vocal stays plain, so the segments come from a second, finished conversion of the stem
+    plain_vocal = "full_vocal" in plan or ("vocal_segments" in plan and finish is None)
+    voc_pk = packed(vocal, state.get("vocal" + st)) if (vocal is not None and plain_vocal) else None
+    voc_seg_pk = voc_pk if finish is None else (
+        PackedTrack.finished(vocal, sr, spans, finish, subtype, hip=hip, dev=state.get("vocal" + st))
+        if (vocal is not None and "vocal_segments" in plan) else None)
+    if "vocal_segments" in plan and voc_seg_pk is not None:
+        exp.vocal_segment_files = exporter.export_spans(voc_seg_pk, out_spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
                                                         file_suffix="_vocal", duration_map=dmap, **naming)
         exp.saved_files += exp.vocal_segment_files
     if "full_vocal" in plan and voc_pk is not None:
@@ -423,6 +457,11 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     if rate_set:        # `output.sample_rate`: what the files are at; `sample_rate` and `cut_points_samples` stay the pipeline's
         out.update({"export_sample_rate": out_sr, "source_sample_rate": source_sr,
                     "export_cut_points_samples": [c if out_sr == sr else map_cut(c, sr, out_sr, n_out, n) for c in cuts]})
+    if finish is not None:      # what was measured and applied, segment by segment
+        out["segment_finish"] = {
+            "settings": finish.as_dict(), "fade_in_frames": finish.fade_in_frames, "fade_out_frames": finish.fade_out_frames,
+            "mix": list(getattr(mix_pk, "finish_rows", [])) if "mix_segments" in plan else [],
+            "vocal": list(getattr(voc_seg_pk, "finish_rows", [])) if ("vocal_segments" in plan and voc_seg_pk is not None) else []}
     if res.get("note"):
         out["note"] = res["note"]
     if smart:       # `:1341-1347`, and the bar analysis behind the cuts
@@ -590,6 +629,8 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
     if result.get("export_sample_rate") is not None:                                      # `output.sample_rate` was set
         manifest["export"] = {"sr": result["export_sample_rate"], "source_sr": result.get("source_sample_rate"),
                               "cuts_samples": result.get("export_cut_points_samples", [])}
+    if result.get("segment_finish") is not None:                                          # fades / normalisation were on
+        manifest["finish"] = result["segment_finish"]
     if result.get("note"):
         manifest["note"] = result["note"]
     for block in ("lyrics_alignment", "boundary_detection", "auto_profile", "intent"):

@@ -76,6 +76,10 @@ DEFAULTS: Dict[str, Any] = {
             "enable": True, "win_ms": 80, "guard_db": 1.5, "search_right_ms": 450,
             "floor_percentile": 0.5, "floor_db_override": None,
         },
+        # segment finishing (utils/segment_finish.py; `expert.yaml:105-107` and the literals of `AudioProcessor.normalize_audio`):
+        # at these defaults the export is what it is without the feature
+        "fade_in_duration": 0.0, "fade_out_duration": 0.0, "normalize_audio": False,
+        "normalize_target_db": -20.0, "normalize_max_gain": 10.0,
     },
     "segment_layout": {"enable": True, "micro_merge_s": 2.0, "soft_min_s": 5.0, "soft_max_s": 12.0, "min_gap_s": 1.0, "beat_snap_ms": 50},
     "vpbd": {

@@ -180,6 +180,16 @@ class PackedTrack:
         return cls.from_bytes(data, int(n_out), channels, int(out_rate), subtype)
 
     @classmethod
+    def finished(cls, audio, sample_rate: int, spans, settings, subtype: str = "PCM_24", *, hip=None, dev=None) -> "PackedTrack":
+        """This track with every span of `spans` finished (`utils/segment_finish.py`: a fade at each end, one gain per span from the
+        RMS of the faded span) and everything outside the spans as the constructor converts it: still a whole-track buffer, so
+        `write(lo, hi)` works as ever.  With a context: the stats launch (when normalising), one launch of `acf_pack_spans` on the
+        device track and one download; without one, `finish_host` + `pcm_bytes_host`.  The result carries `finish_rows`, one dict
+        per span (`gain`, `gain_db`, `rms_db`, `peak_out`, `clipped`)."""
+        from .segment_finish import finished
+        return finished(audio, sample_rate, spans, settings, subtype, hip=hip, dev=dev)
+
+    @classmethod
     def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
         """`from_bytes` for PCM_24."""
         return cls.from_bytes(data, n, channels, sample_rate, "PCM_24")
