@@ -24,6 +24,8 @@ channel mean is `librosa.load(mono=True)`'s; a float file holding a NaN or an in
 available offline, so this row's parity definition is the scipy filter — SURVEY.md §8(f) row 2).
 Export (`seamless_splitter.py:674-731`): `segment_NNN_{human|music}_D.D.wav` mix segments, `segments_vocal/..._vocal_D.D.wav`,
 `<name>_<mode>_vocal_full_D.D.wav`, `<name>_<mode>_instrumental_D.D.wav`, all of the subtype `output.wav.subtype` names (default PCM_24), packed on the GPU (`ac_pack_pcm`).
+With `output.format: flac` the same files are `.flac`: the packed bytes stay on the device and are encoded there (`utils/flac_export.py`,
+`_flac_native.py`), decoding to exactly the samples of the WAV of that subtype; the result then carries `export_format`.
 `output.sample_rate` (`"source"` or an integer; absent by default; INTEGRATION.md, "Export rate") lets the files leave at another rate than
 `audio.sample_rate`: the stems through `ac_resample_poly_pack` (`utils/rate_export.py`), the mix at the file's own rate as it was loaded.
 Manifest: `_build_manifest` (`api.py:178-263`) key for key, QA report included, and the lyrics attachment to segments where an alignment
@@ -198,13 +200,14 @@ def _export_vocal_separation(res: Mapping[str, Any], in_path: Path, out_dir: Pat
     plan = _vocal_separation_plan(export_types)
     pcm = res["stem_pcm24"]
     subtype = pcm.get("subtype", "PCM_24")
+    flac = pcm.get("flac")                  # `output.format: flac`: the stems are device tensors, encoded there
     seconds = int(pcm["n"]) / float(sr)
     exporter = SegmentExporter(sr)
     files: Dict[str, Optional[str]] = {"vocal": None, "instrumental": None}
     saved = []
     for kind in ("vocal", "instrumental"):
         if f"full_{kind}" in plan and pcm.get(kind) is not None:      # no instrumental: the reference logs it and goes on (`:1007-1008`)
-            track = PackedTrack.from_bytes(pcm[kind], int(pcm["n"]), int(pcm["channels"]), sr, subtype)
+            track = PackedTrack.from_bytes(pcm[kind], int(pcm["n"]), int(pcm["channels"]), sr, subtype, flac=flac, hip=pcm.get("hip"))
             files[kind] = exporter.export_full_track(track, out_dir / f"{in_path.stem}_{kind}_{seconds:.1f}")
             saved.append(files[kind])
     out: Dict[str, Any] = {
@@ -216,6 +219,8 @@ def _export_vocal_separation(res: Mapping[str, Any], in_path: Path, out_dir: Pat
         "precision_guard_ok": bool(res["precision_guard_ok"]), "precision_guard_threshold_ms": dict(res["precision_guard_threshold_ms"]),
         "input_file": str(in_path), "output_dir": str(out_dir), "sample_rate": sr, "timings": res.get("timings", {}),
     }
+    if flac is not None:
+        out["export_format"] = "flac"
     out.update(res.get("gpu_meta", {}))
     return out
 
@@ -313,9 +318,13 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     split, export, and the result dict `_build_manifest` reads.  `channels == 2`: the planar stereo track is split (true-stereo
     separation, detection on its channel mean) and every file is written with both channels."""
     import time
-    from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter, configured_subtype
+    from .utils.audio_export import ExportResult, PackedTrack, SegmentExporter, configured_flac_options, configured_subtype
     t_start = time.time()
     subtype = configured_subtype()          # `output.format` / `output.wav.subtype`: refused here, before any work, if not written
+    # `output.format: flac` (utils/flac_export.py): the checked `output.flac` settings, else None - and then every call below is
+    # the call of a build without the format
+    flac = configured_flac_options()
+    fkw = {} if flac is None else {"flac": flac}
     finish = _configured_finish(sr)         # segment finishing (utils/segment_finish.py); None with the keys at their defaults
     # `output.sample_rate` (utils/rate_export.py): the rate the files leave at, resolved - and refused - from the file's header
     # alone, before the track is loaded.  Absent: `out_sr` is `sr` and nothing below differs from a build without the setting.
@@ -395,7 +404,7 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         n_out, out_spans = n, spans
 
         def packed(track, dev):
-            return PackedTrack(track, sr, subtype, hip=hip, dev=dev)
+            return PackedTrack(track, sr, subtype, hip=hip, dev=dev, **fkw)
     else:
         # every exported track has n_out frames: the file's own count at the file's rate (the stems are cropped to it, never padded),
         # else what the resampler gives; every span end goes to its nearest frame there and the end of the track to n_out, so the
@@ -404,13 +413,13 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         out_spans = [(map_cut(lo, sr, out_sr, n_out, n), map_cut(hi, sr, out_sr, n_out, n)) for lo, hi in spans]
 
         def packed(track, dev):
-            return PackedTrack.resampled(track, sr, out_sr, n_out, subtype, hip=hip, dev=dev)
+            return PackedTrack.resampled(track, sr, out_sr, n_out, subtype, hip=hip, dev=dev, **fkw)
     if "mix_segments" in plan:
         if finish is not None:              # out_sr == sr here: the spans are finished where the track becomes bytes
-            mix_pk = PackedTrack.finished(audio, sr, spans, finish, subtype, hip=hip, dev=mix_dev)
+            mix_pk = PackedTrack.finished(audio, sr, spans, finish, subtype, hip=hip, dev=mix_dev, **fkw)
         elif source_track is not None:      # the loaded track as it was in front of the load resampler: nothing is resampled twice
             is_dev = not isinstance(source_track, np.ndarray)
-            mix_pk = PackedTrack(source_track, out_sr, subtype, hip=hip, dev=source_track if is_dev else None)
+            mix_pk = PackedTrack(source_track, out_sr, subtype, hip=hip, dev=source_track if is_dev else None, **fkw)
         else:
             mix_pk = packed(audio, mix_dev)
         exp.mix_segment_files = exporter.export_spans(mix_pk, out_spans, str(out_dir), segment_is_vocal=flags, duration_map=dmap,
@@ -421,8 +430,10 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
     plain_vocal = "full_vocal" in plan or ("vocal_segments" in plan and finish is None)
     voc_pk = packed(vocal, state.get("vocal" + st)) if (vocal is not None and plain_vocal) else None
     voc_seg_pk = voc_pk if finish is None else (
-        PackedTrack.finished(vocal, sr, spans, finish, subtype, hip=hip, dev=state.get("vocal" + st))
+        PackedTrack.finished(vocal, sr, spans, finish, subtype, hip=hip, dev=state.get("vocal" + st), **fkw)
         if (vocal is not None and "vocal_segments" in plan) else None)
+    if flac is not None and voc_pk is not None and voc_seg_pk is voc_pk and "vocal_segments" in plan and "full_vocal" in plan:
+        voc_pk.prepare(list(out_spans) + [(0, voc_pk.n)])      # the segments and the full stem in one encoder call
     if "vocal_segments" in plan and voc_seg_pk is not None:
         exp.vocal_segment_files = exporter.export_spans(voc_seg_pk, out_spans, str(out_dir), segment_is_vocal=flags, subdir="segments_vocal",
                                                         file_suffix="_vocal", duration_map=dmap, **naming)
@@ -454,6 +465,8 @@ def _split_and_export(in_path: Path, out_dir: Path, mode: str, export_types: Opt
         "full_instrumental_file": exp.full_instrumental_file,
         "timings": res.get("timings", {}), "processing_time": time.time() - t_start,
     }
+    if flac is not None:        # only when the files are not WAV
+        out["export_format"] = "flac"
     if rate_set:        # `output.sample_rate`: what the files are at; `sample_rate` and `cut_points_samples` stay the pipeline's
         out.update({"export_sample_rate": out_sr, "source_sample_rate": source_sr,
                     "export_cut_points_samples": [c if out_sr == sr else map_cut(c, sr, out_sr, n_out, n) for c in cuts]})
@@ -629,6 +642,8 @@ def _build_manifest(*, result: Mapping[str, Any], input_path: Path, export_dir: 
     if result.get("export_sample_rate") is not None:                                      # `output.sample_rate` was set
         manifest["export"] = {"sr": result["export_sample_rate"], "source_sr": result.get("source_sample_rate"),
                               "cuts_samples": result.get("export_cut_points_samples", [])}
+    if result.get("export_format") is not None:                                           # `output.format` was not `wav`
+        manifest["export_format"] = result["export_format"]
     if result.get("segment_finish") is not None:                                          # fades / normalisation were on
         manifest["finish"] = result["segment_finish"]
     if result.get("note"):

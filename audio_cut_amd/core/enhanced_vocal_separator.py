@@ -380,14 +380,16 @@ class EnhancedVocalSeparator:
         torch.cuda.current_stream(hip.device).synchronize()
         h2d_ms = (time.perf_counter() - t0) * 1000.0
 
-        from ..utils.audio_export import configured_subtype
+        from ..utils.audio_export import configured_flac_options, configured_subtype
         subtype = configured_subtype()
+        flac = configured_flac_options()          # `output.format: flac`: the stems stay on the device for the encoder
         sep = backend.separate_track(track_dev, sr, gpu_context.plans, timings, defer_sync=True, export_pcm24=True, export_subtype=subtype)
         t1 = time.perf_counter()
-        vocal_h = torch.empty(sep.vocal.shape, dtype=torch.uint8, pin_memory=True)
-        inst_h = torch.empty(sep.instrumental.shape, dtype=torch.uint8, pin_memory=True)
-        vocal_h.copy_(sep.vocal, non_blocking=True)
-        inst_h.copy_(sep.instrumental, non_blocking=True)
+        if flac is None:
+            vocal_h = torch.empty(sep.vocal.shape, dtype=torch.uint8, pin_memory=True)
+            inst_h = torch.empty(sep.instrumental.shape, dtype=torch.uint8, pin_memory=True)
+            vocal_h.copy_(sep.vocal, non_blocking=True)
+            inst_h.copy_(sep.instrumental, non_blocking=True)
         gpu_context.capture_device_metrics()      # as in the detection path: taken while the host waits for the U-Net anyway
         sep.finish()
         ve, ie, me = (float(np.sum(row)) / float(total) for row in sep.energy_partials.cpu().numpy())    # partials added in index order
@@ -406,8 +408,12 @@ class EnhancedVocalSeparator:
         gm["gpu_pipeline_chunk_invocations"] = len(sep.chunk_ranges)
         gm["mdx23_output_type"] = backend.get_output_type()
         gm["gpu_pipeline_stage_ms"] = dict(timings)
-        pcm = {"vocal": vocal_h.numpy(), "instrumental": inst_h.numpy() if has_inst else None, "channels": 2 if stereo else 1, "n": total,
-               "subtype": subtype}
+        if flac is None:
+            pcm = {"vocal": vocal_h.numpy(), "instrumental": inst_h.numpy() if has_inst else None, "channels": 2 if stereo else 1, "n": total,
+                   "subtype": subtype}
+        else:                                     # device tensors, and what the encoder needs to reach them
+            pcm = {"vocal": sep.vocal, "instrumental": sep.instrumental if has_inst else None, "channels": 2 if stereo else 1, "n": total,
+                   "subtype": subtype, "flac": flac, "hip": hip}
         return pcm, confidence
 
     def _side_stream(self, hip) -> "torch.cuda.Stream":

@@ -9,6 +9,8 @@ clipping conversion - python-soundfile sets SFC_SET_CLIPPING on every file, so `
 whole word for PCM_32); FLOAT is the float32 bits as they are and DOUBLE their exact widening, nothing clipped.  Segment files are
 byte slices of that buffer behind a RIFF header (44 bytes for the integer subtypes, 56 with the `fact` chunk of the float ones).
 MP3 needs pydub + FFmpeg in the reference (`:114-135`) and is refused here.
+FLAC (`output.format: flac`, this build's own) is encoded from the same sample bytes - on the device when they are there - and
+decodes to exactly the WAV's integer samples: `PackedTrack`'s FLAC form, `utils/flac_export.py`, `_flac_native.py`.
 Stereo tracks are planar (2, N) arrays (the reference writes `(channels, samples)` arrays as multichannel files, `:93-106`): they
 are interleaved frame by frame in the packing kernel, which reads the planar rows as they are, and the header carries two channels.
 """
@@ -21,7 +23,9 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-_DEFAULTS: Dict[str, Dict[str, object]] = {"wav": {"subtype": "PCM_24"}}
+# `output.<format>` defaults.  The FLAC ones live here, not in `config.DEFAULTS`: `output.flac.subtype` (PCM_16 or PCM_24),
+# `output.flac.block_size` (256..4096) and `output.flac.md5` (`utils/flac_export.py`)
+_DEFAULTS: Dict[str, Dict[str, object]] = {"wav": {"subtype": "PCM_24"}, "flac": {"subtype": "PCM_24", "block_size": 4096, "md5": False}}
 
 
 # subtype -> (AC_PACK_* code of include/audiocut_hip_pack.h, bytes per word)
@@ -57,9 +61,21 @@ def configured_subtype() -> str:
     over the format's defaults, as the reference's splitter reads them (`seamless_splitter.py:98-103,167-192`)."""
     from ..config import get_config
     fmt = ensure_supported_format(get_config("output.format", "wav"))
+    if fmt == "flac":                       # FLAC's own two subtypes, block size and MD5 switch, each refused by name
+        from .flac_export import configured_flac
+        return str(configured_flac()["subtype"])
     subtype = build_export_options(fmt, get_config(f"output.{fmt}", {}) or {}).get("subtype", "PCM_24")
     subtype_info(subtype)
     return str(subtype)
+
+
+def configured_flac_options() -> Optional[Dict[str, object]]:
+    """The checked `output.flac` settings when `output.format` is `flac`, else None - and then nothing of FLAC is imported."""
+    from ..config import get_config
+    if ensure_supported_format(get_config("output.format", "wav")) != "flac":
+        return None
+    from .flac_export import configured_flac
+    return configured_flac()
 
 
 def _export_path(base_path: Path, ext: str) -> Path:
@@ -134,36 +150,58 @@ def _channels_of(audio) -> int:
 
 class PackedTrack:
     """A whole mono [N] or planar stereo (2, N) track converted once (on the GPU when a context and device tensor are given);
-    slices are cheap.  Stereo frames are interleaved (L, R) like every multichannel WAV.  `subtype`: one of `WAV_SUBTYPES`."""
+    slices are cheap.  Stereo frames are interleaved (L, R) like every multichannel WAV.  `subtype`: one of `WAV_SUBTYPES`.
 
-    def __init__(self, audio: np.ndarray, sample_rate: int, subtype: str = "PCM_24", *, hip=None, dev=None) -> None:
+    The FLAC form (`flac`: the checked settings of `flac_export.checked_options`, None for WAV): the same sample bytes, which
+    with a context STAY a device tensor; `prepare(spans)` encodes the spans to be written in one `FlacKernels.encode` call (two
+    launches, one download of the compressed stream; the PCM bytes are downloaded only for `md5`) and `write` emits the
+    STREAMINFO header and that span's frames.  Without a context the bytes are host bytes and `flac_encode_host` encodes them."""
+
+    flac: Optional[Dict[str, object]] = None
+    hip = None
+
+    def __init__(self, audio: np.ndarray, sample_rate: int, subtype: str = "PCM_24", *, hip=None, dev=None,
+                 flac: Optional[Dict[str, object]] = None) -> None:
         subtype_info(subtype)
+        if flac is not None:
+            self._set_flac(flac, subtype, hip)
         self.sample_rate = int(sample_rate)
         self.subtype = subtype
         self.channels = _channels_of(np.asarray(audio) if dev is None else dev)
         self.n = int(np.shape(audio)[-1])
         if hip is not None and self.n > 0:                  # the planar track as it is, interleaved in the kernel
             d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
-            self.bytes, self.width = hip.pack_pcm(d, subtype), subtype_info(subtype)[1]
+            self.bytes = hip.pack_pcm(d, subtype) if flac is None else hip.pack_pcm_device(d, subtype)
+            self.width = subtype_info(subtype)[1]
         else:
             x = np.asarray(audio)
             self.bytes, self.width = pcm_bytes_host(x.T if self.channels == 2 else x, subtype)
 
     @classmethod
-    def from_bytes(cls, data, n: int, channels: int, sample_rate: int, subtype: str) -> "PackedTrack":
+    def from_bytes(cls, data, n: int, channels: int, sample_rate: int, subtype: str, *, flac: Optional[Dict[str, object]] = None,
+                   hip=None) -> "PackedTrack":
         """Wrap sample bytes of `subtype` that are ready (`ac_mdx_assemble_pcm`): `width * channels * n` of them, stereo frames
-        interleaved L, R - the layout the constructor produces."""
+        interleaved L, R - the layout the constructor produces.  The FLAC form with a context takes them as a uint8 device tensor."""
         width = subtype_info(subtype)[1]
-        data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, dtype=np.uint8).reshape(-1)
-        if channels not in (1, 2) or n < 0 or data.size != width * channels * n:
-            raise ValueError(f"expected {width * channels * n} {subtype} bytes for {n} frames of {channels} channel(s), got {data.size}")
+        on_device = flac is not None and hip is not None and not isinstance(data, (bytes, bytearray, memoryview, np.ndarray))
+        if on_device:
+            data = data.reshape(-1)
+            size = int(data.numel())
+        else:
+            data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.asarray(data, dtype=np.uint8).reshape(-1)
+            size = int(data.size)
+        if channels not in (1, 2) or n < 0 or size != width * channels * n:
+            raise ValueError(f"expected {width * channels * n} {subtype} bytes for {n} frames of {channels} channel(s), got {size}")
         track = cls.__new__(cls)
+        if flac is not None:
+            track._set_flac(flac, subtype, hip)
         track.sample_rate, track.subtype, track.channels, track.n = int(sample_rate), subtype, int(channels), int(n)
         track.bytes, track.width = data, width
         return track
 
     @classmethod
-    def resampled(cls, audio, sample_rate: int, out_rate: int, n_out: int, subtype: str = "PCM_24", *, hip=None, dev=None) -> "PackedTrack":
+    def resampled(cls, audio, sample_rate: int, out_rate: int, n_out: int, subtype: str = "PCM_24", *, hip=None, dev=None,
+                  flac: Optional[Dict[str, object]] = None) -> "PackedTrack":
         """This track (at `sample_rate`), resampled to `out_rate` and cropped to `n_out` frames (`output.sample_rate`): with a
         context, one launch of `ac_resample_poly_pack` on the device track (`utils/rate_export.py`) and one download of the
         finished bytes - no float track at `out_rate` exists anywhere; without one, `resample_pack_host`.  `sample_rate` of the
@@ -174,27 +212,80 @@ class PackedTrack:
         channels = _channels_of(np.asarray(audio) if dev is None else dev)
         if hip is not None:
             d = dev if dev is not None else hip.to_device(np.ascontiguousarray(audio, dtype=np.float32))
-            data = resample_pack_device(hip, d, up, down, subtype, int(n_out)).cpu().numpy()
+            data = resample_pack_device(hip, d, up, down, subtype, int(n_out))
+            data = data.cpu().numpy() if flac is None else data.contiguous()       # FLAC: the bytes stay on the device
         else:
             data = resample_pack_host(np.asarray(audio), up, down, subtype, int(n_out))
-        return cls.from_bytes(data, int(n_out), channels, int(out_rate), subtype)
+        return cls.from_bytes(data, int(n_out), channels, int(out_rate), subtype, flac=flac, hip=hip)
 
     @classmethod
-    def finished(cls, audio, sample_rate: int, spans, settings, subtype: str = "PCM_24", *, hip=None, dev=None) -> "PackedTrack":
+    def finished(cls, audio, sample_rate: int, spans, settings, subtype: str = "PCM_24", *, hip=None, dev=None,
+                 flac: Optional[Dict[str, object]] = None) -> "PackedTrack":
         """This track with every span of `spans` finished (`utils/segment_finish.py`: a fade at each end, one gain per span from the
         RMS of the faded span) and everything outside the spans as the constructor converts it: still a whole-track buffer, so
         `write(lo, hi)` works as ever.  With a context: the stats launch (when normalising), one launch of `acf_pack_spans` on the
         device track and one download; without one, `finish_host` + `pcm_bytes_host`.  The result carries `finish_rows`, one dict
         per span (`gain`, `gain_db`, `rms_db`, `peak_out`, `clipped`)."""
         from .segment_finish import finished
-        return finished(audio, sample_rate, spans, settings, subtype, hip=hip, dev=dev)
+        return finished(audio, sample_rate, spans, settings, subtype, hip=hip, dev=dev, flac=flac)
 
     @classmethod
     def from_pcm24(cls, data, n: int, channels: int, sample_rate: int) -> "PackedTrack":
         """`from_bytes` for PCM_24."""
         return cls.from_bytes(data, n, channels, sample_rate, "PCM_24")
 
+    # -- the FLAC form ------------------------------------------------------------------------------------------------------
+    def _set_flac(self, flac: Dict[str, object], subtype: str, hip) -> None:
+        from .flac_export import checked_options, flac_subtype_width
+        self.flac = checked_options(flac)
+        flac_subtype_width(subtype)             # PCM_16 or PCM_24: the words FLAC frames are made of here
+        self.hip = hip
+        self._flac_files: Dict[Tuple[int, int], bytes] = {}
+
+    @property
+    def ext(self) -> str:
+        """The extension of the files this track writes."""
+        return "wav" if self.flac is None else "flac"
+
+    def _clamped(self, start: int, end: Optional[int]) -> Tuple[int, int]:
+        end = self.n if end is None else end
+        start = max(0, min(int(start), self.n))
+        return start, max(start, min(int(end), self.n))
+
+    def prepare(self, spans) -> None:
+        """FLAC form: encode every span of `spans` that `write` will be asked for, all in one call (a WAV track does nothing)."""
+        if self.flac is None:
+            return
+        todo = []
+        for lo, hi in spans:
+            key = self._clamped(lo, hi)
+            if key[1] > key[0] and key not in self._flac_files and key not in todo:
+                todo.append(key)
+        if not todo:
+            return
+        block, md5 = int(self.flac["block_size"]), bool(self.flac["md5"])
+        if isinstance(self.bytes, np.ndarray):
+            from .flac_export import flac_encode_host
+            files = flac_encode_host(self.bytes, self.n, self.channels, self.width, self.sample_rate, todo, block, md5)
+        else:
+            from .._flac_native import FlacKernels
+            files = FlacKernels(self.hip).encode(self.bytes, self.n, self.channels, self.width, self.sample_rate, todo, block, md5)
+        self._flac_files.update(zip(todo, files))
+
+    def _write_flac(self, path: Path, start: int, end: int) -> Path:
+        from .flac_export import flac_header
+        if end == start:                        # no samples: STREAMINFO alone
+            data = flac_header(self.sample_rate, self.channels, 8 * self.width, 0, int(self.flac["block_size"]), 0, 0)
+        else:
+            self.prepare([(start, end)])
+            data = self._flac_files.pop((start, end))
+        with open(path, "wb") as fh:
+            fh.write(data)
+        return Path(path)
+
     def write(self, path: Path, start: int = 0, end: Optional[int] = None) -> Path:
+        if self.flac is not None:
+            return self._write_flac(path, *self._clamped(start, end))
         end = self.n if end is None else end
         start = max(0, min(int(start), self.n)); end = max(start, min(int(end), self.n))
         frame = self.width * self.channels
@@ -211,7 +302,7 @@ def export_audio(audio: np.ndarray, sample_rate: int, base_path: Path, format_na
     path = _export_path(Path(base_path), key)
     arr = np.asarray(audio)
     _channels_of(arr)
-    PackedTrack(arr, sample_rate, str(opts.get("subtype", "PCM_24"))).write(path)
+    PackedTrack(arr, sample_rate, str(opts.get("subtype", "PCM_24")), flac=opts if key == "flac" else None).write(path)
     return path
 
 
@@ -267,11 +358,12 @@ class SegmentExporter:
         base = Path(output_dir) / subdir if subdir else Path(output_dir)
         base.mkdir(parents=True, exist_ok=True)
         saved: List[str] = []
+        track.prepare(spans)                    # the FLAC form encodes all of them in one call
         for i, (lo, hi) in enumerate(spans):
             stem = self._stem(i, hi - lo, track.sample_rate, segment_is_vocal=segment_is_vocal, lib_flags=lib_flags,
                               lib_suffix=lib_suffix, file_suffix=file_suffix, duration_map=duration_map, index_offset=index_offset,
                               always_append_duration=always_append_duration)
-            saved.append(str(track.write(_export_path(base / stem, "wav"), lo, hi)))
+            saved.append(str(track.write(_export_path(base / stem, track.ext), lo, hi)))
         return saved
 
     def export_full_track(self, audio, output_base: Path, *, export_format: str = "wav",
@@ -279,9 +371,10 @@ class SegmentExporter:
         """`audio`: a PackedTrack (device path) or a mono array (the reference's form)."""
         Path(output_base).parent.mkdir(parents=True, exist_ok=True)
         if isinstance(audio, PackedTrack):
-            return str(audio.write(_export_path(Path(output_base), ensure_supported_format(export_format))))
+            ensure_supported_format(export_format)
+            return str(audio.write(_export_path(Path(output_base), audio.ext)))
         return str(export_audio(audio, self.sample_rate, Path(output_base), export_format, options=export_options))
 
 
 __all__ = ["ensure_supported_format", "build_export_options", "export_audio", "ExportResult", "SegmentExporter", "PackedTrack",
-           "wav_header", "wav_pad", "pcm_bytes_host", "WAV_SUBTYPES", "subtype_info", "configured_subtype"]
+           "wav_header", "wav_pad", "pcm_bytes_host", "WAV_SUBTYPES", "subtype_info", "configured_subtype", "configured_flac_options"]

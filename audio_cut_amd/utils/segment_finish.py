@@ -160,10 +160,11 @@ def finish_rows(sumsq, peak, gains, lengths: Sequence[int], channels: int, subty
     return rows
 
 
-def finished(audio, sample_rate: int, spans, settings: FinishSettings, subtype: str, *, hip=None, dev=None) -> PackedTrack:
+def finished(audio, sample_rate: int, spans, settings: FinishSettings, subtype: str, *, hip=None, dev=None, flac=None) -> PackedTrack:
     """`PackedTrack.finished`: the whole track converted once, its spans finished.  With a context: the stats launch (only when
     normalising, else the gains are 1 and nothing is measured), the gains on the host, one launch of `acf_pack_spans`, one download.
-    Without one: `finish_host` and `pcm_bytes_host`.  The track carries `finish_rows`."""
+    Without one: `finish_host` and `pcm_bytes_host`.  The track carries `finish_rows`.  `flac`: the FLAC form of the track
+    (`PackedTrack`), whose finished bytes stay on the device."""
     subtype_info(subtype)
     channels = _channels_of(np.asarray(audio) if dev is None else dev)
     n = int(np.shape(audio)[-1])
@@ -180,7 +181,7 @@ def finished(audio, sample_rate: int, spans, settings: FinishSettings, subtype: 
         if settings.normalize_audio:
             sumsq, peak = kernels.span_stats(d, sp, fi, fo)
             gains = np.array([gain_from_stats(ss, length * channels, settings) for ss, length in zip(sumsq, lengths)], dtype=np.float32)
-        data = kernels.pack_spans(d, sp, gains, fi, fo, subtype)
+        data = kernels.pack_spans(d, sp, gains, fi, fo, subtype) if flac is None else kernels.pack_spans_device(d, sp, gains, fi, fo, subtype)
     else:
         x = np.asarray(audio, dtype=np.float32)
         if settings.normalize_audio:
@@ -188,7 +189,7 @@ def finished(audio, sample_rate: int, spans, settings: FinishSettings, subtype: 
             gains = np.array([gain_from_stats(ss, length * channels, settings) for ss, length in zip(sumsq, lengths)], dtype=np.float32)
         y = finish_host(x, sp, gains, fi, fo)
         data, _ = pcm_bytes_host(y.T if channels == 2 else y, subtype)
-    track = PackedTrack.from_bytes(data, n, channels, int(sample_rate), subtype)
+    track = PackedTrack.from_bytes(data, n, channels, int(sample_rate), subtype, flac=flac, hip=hip)
     track.finish_rows = finish_rows(sumsq, peak, gains, lengths, channels, subtype)
     return track
 
